@@ -1,6 +1,7 @@
 """Headline benchmark: GPT training throughput on N MI355X GPUs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--parallel dp|tp|pp] [--tp T] [--model gpt2-small|ref|gpt2-medium]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): avg step time (ms) + tokens/sec of **GPT-2 small** (the model every
 BASELINE.json config names: d_model 768, 12 layers, 12 heads, d_ff 3072, seq 1024, vocab 50258,
@@ -14,16 +15,26 @@ GPT-2 small that comparator is conservative: GPT-2 small costs ~2.8x the FLOPs p
 reference model (854 M vs 302 M FLOP/token, fwd+bwd), so its tokens/s would be lower on the
 reference's own hardware.  The JSON names the comparator (``baseline_comparator``).
 
-Timed span.  W untimed warmup steps first (the first one eager, then hipGraph capture), then TWO
-timed loops of K steps, each bracketed by barrier + device sync on both sides, MAX over ranks:
+Timed span.  W untimed warmup steps first (the first one eager, then hipGraph capture), then the
+timed loop of K steps, bracketed by barrier + device sync on both sides, MAX over ranks.  A plain run
+does nothing else: set up, warm up, time the K blocking steps, write ``--dump-outputs``, print the JSON
+line.  ``--full`` adds a second timed loop of K steps (pipelined) and the ``ref_fp32`` point after it:
 
 * **blocking** -- ``value`` / ``ms_per_step``: the reference's timed loop (``train/train.py:75-85``)
   step for step: next host batch -> H2D -> full forward + backward + gradient collectives + clip +
   AdamW -> blocking read of THIS step's loss before the next step is issued.  The next batch's host
   work (pinned-buffer fill, embedding sort keys: ``Engine.stage_batch``) runs while the step is on the
   GPU, as a host data loader's would; its H2D copies and the next launch come after the loss read;
-* **pipelined** -- ``ms_per_step_pipelined``: the same steps, but step i's loss is read after step
-  i+1 is enqueued (the host never leaves the GPU idle between steps; every loss is still read).
+* **pipelined** (``--full``) -- ``ms_per_step_pipelined``: the same steps, but step i's loss is read after
+  step i+1 is enqueued (the host never leaves the GPU idle between steps; every loss is still read);
+* **ref_fp32** (``--full``, 1 GPU; ``--ref32 on`` forces it) -- the reference's own model at the reference's
+  precision, next to the published number (:func:`_ref_fp32_point`).
+
+``--dump-outputs DIR`` writes what the blocking loop's last step handed back (rank 0), as ``DIR/<name>.npy``:
+``loss`` and ``grad_norm`` (float64 scalars), ``loss_history`` (float64 [K], every timed step's loss) and
+``params_sample`` (float32: the fp32 master parameters after the last AdamW update, at up to 4 Mi flat
+indices drawn once from a fixed seed; all of them if the model has fewer).  Weights, tokens and the sample
+are pure functions of the arguments, so two builds can be compared output for output.
 
 ``value`` is whole-job tokens/s of the blocking loop.  ``tflops_per_gpu`` counts the causal
 attention's useful FLOPs (``ModelConfig.flops_per_token``).
@@ -113,6 +124,28 @@ def _ref_fp32_point(dinfo, steps: int = 20, warmup: int = 3):
             "reference_ms_per_step": 146.88, "vs_reference": round(tok / BASELINE_TOKENS_PER_S["dp"], 3)}
 
 
+DUMP_PARAMS = 1 << 22  # --dump-outputs: flat fp32 parameters sampled (16 MB)
+
+
+def _dump_outputs(eng, out_dir: str, losses):
+    """``--dump-outputs``: the last timed step's loss, gradient norm and (a fixed sample of) the updated
+    parameters, plus every timed step's loss."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    params = eng.flat.params
+    n = params.numel()
+    if n > DUMP_PARAMS:
+        idx = np.sort(np.random.default_rng(0).integers(0, n, size=DUMP_PARAMS, dtype=np.int64))
+        params = params[torch.from_numpy(idx).to(params.device)]
+    torch.cuda.synchronize()
+    np.save(os.path.join(out_dir, "params_sample.npy"), params.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(losses[-1], dtype=np.float64))
+    np.save(os.path.join(out_dir, "loss_history.npy"), np.asarray(losses, dtype=np.float64))
+    np.save(os.path.join(out_dir, "grad_norm.npy"), np.asarray(eng.grad_norm(), dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -129,7 +162,13 @@ def main():
     ap.add_argument("--pp_schedule", default="zb", choices=["gpipe", "1f1b", "zb"])
     ap.add_argument("--ref32", default="auto", choices=["auto", "on", "off"],
                     help="also time the reference's own model (d512 L12 T512) at the reference's precision (exact "
-                         "fp32) and report it as ref_fp32 next to the headline (auto: on for a 1-GPU run)")
+                         "fp32) and report it as ref_fp32 next to the headline (auto: on for a 1-GPU --full run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also time the pipelined loop (ms_per_step_pipelined) and the "
+                         "ref_fp32 point; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (loss, grad_norm, loss_history, params_sample) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="extra TrainConfig overrides for A/B runs, e.g. --set defer_optimizer=false")
     args = ap.parse_args()
@@ -178,7 +217,7 @@ def main():
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        loss = float("nan")
+        losses = []
         pending = None
         eng.stage_batch(next(data))
         for i in range(args.steps):
@@ -190,21 +229,24 @@ def main():
                 # step runs; its H2D copies are enqueued only after the loss read.  The pinned slot it fills was
                 # last copied from before step i-1, whose loss was read.
                 eng.stage_batch(next(data))
-                loss = eng.read_loss(handle)
+                losses.append(eng.read_loss(handle))
                 continue
             if pending is not None:  # step i-1's loss, read with step i already enqueued
-                loss = eng.read_loss(pending)
+                losses.append(eng.read_loss(pending))
             pending = handle
             eng.stage_batch(next(data))  # after step i-1's read: its pinned slot's copy has landed
         if pending is not None:
-            loss = eng.read_loss(pending)
+            losses.append(eng.read_loss(pending))
         eng.flush_optimizer()  # a deferred last AdamW lands inside the timed region
         torch.cuda.synchronize()
         barrier()
-        return time.perf_counter() - t0, loss
+        return time.perf_counter() - t0, losses
 
-    dt_pipe, _ = timed(True)
-    dt, loss = timed(False)
+    dt, losses = timed(False)
+    loss = losses[-1] if losses else float("nan")
+    if args.dump_outputs and dinfo.rank == 0:
+        _dump_outputs(eng, args.dump_outputs, losses)
+    dt_pipe = timed(True)[0] if args.full else 0.0
     healthy = 1.0
     try:  # device-side wait timeouts (P2P flags, fused LayerNorm statistics): the timed steps computed NaN
         eng.check_health()
@@ -237,7 +279,7 @@ def main():
         out = {
             "metric": metric, "value": round(value, 1), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
             "warmup": warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": scaling,
-            "ms_per_step_pipelined": round(1e3 * dt_pipe / args.steps, 4), "timed_span": "blocking per-step loss read",
+            "timed_span": "blocking per-step loss read", "full": args.full,
             "vs_baseline": round(value / base, 3) if base else None, "dtype": tc.dtype,
             "data": "synthetic (FineWeb-shaped token stream, random-init weights)",
             "healthy": bool(healthy),
@@ -257,17 +299,20 @@ def main():
                        "baseline_comparator": (f"reference 89.6M model, fp32, {args.parallel.upper()} "
                                                f"{BASELINE_TOKENS_PER_S.get(args.parallel):,.0f} tok/s (BASELINE.md)")},
         }
+        if args.full:
+            out["ms_per_step_pipelined"] = round(1e3 * dt_pipe / args.steps, 4)
     # the like-for-like point: the reference's own model and precision (fp32) on this GPU, timed after the
     # headline engine is released
     del eng, data
     gc.collect()
     torch.cuda.empty_cache()
-    if args.ref32 == "on" or (args.ref32 == "auto" and world == 1 and args.model != "ref"):
+    if args.ref32 == "on" or (args.full and args.ref32 == "auto" and world == 1 and args.model != "ref"):
         ref32 = _ref_fp32_point(dinfo)
     else:
         ref32 = None
     if dinfo.rank == 0:
-        out["ref_fp32"] = ref32
+        if args.full or ref32 is not None:
+            out["ref_fp32"] = ref32
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
