@@ -3,6 +3,9 @@ fused single-round kernel (default) vs the two-round resident kernels (flags bit
 rounds, plus the forward.  Also checks that both backward variants agree.
 
     python benchmarks/attn_ab.py [--rounds 7] [--reps 50]
+
+--shape hd128: the head_dim 128 kernels at the gpt-1.3b layer (B8 T1024 H16 hd128) against the shipped head_dim 64
+kernels at B8 T1024 H32 hd64 (same d_model, same attention FLOPs, same bytes), interleaved in one process.
 """
 import argparse
 import os
@@ -41,9 +44,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--shape", default="gpt2s", choices=["ref", "gpt2s"])
+    ap.add_argument("--shape", default="gpt2s", choices=["ref", "gpt2s", "hd128"])
     a = ap.parse_args()
-    B, T, H, hd = (8, 512, 16, 32) if a.shape == "ref" else (8, 1024, 12, 64)
+    B, T, H, hd = {"ref": (8, 512, 16, 32), "gpt2s": (8, 1024, 12, 64), "hd128": (8, 1024, 16, 128)}[a.shape]
     g = torch.Generator().manual_seed(0)
     qkv = torch.randn(B, T, 3 * H * hd, generator=g).cuda().bfloat16()
     do = torch.randn(B, T, H * hd, generator=g).cuda().bfloat16()
@@ -53,6 +56,12 @@ def main():
         variants = {"fwd": lambda: A.attn_fwd(qkv, H), "fwd plain order": lambda: A.attn_fwd(qkv, H, flags=1),
                     "bwd fused": lambda: A.attn_bwd(qkv, o, lse, do, H),
                     "bwd two-round": lambda: A.attn_bwd(qkv, o, lse, do, H, flags=1)}
+    elif a.shape == "hd128":
+        H64 = 2 * H  # the yardstick: same d_model, FLOPs and bytes at head_dim 64 (same buffers, re-viewed)
+        o64, lse64 = A.attn_fwd(qkv, H64)
+        variants = {"fwd hd128": lambda: A.attn_fwd(qkv, H), "fwd hd64 (H x 2)": lambda: A.attn_fwd(qkv, H64),
+                    "bwd hd128": lambda: A.attn_bwd(qkv, o, lse, do, H),
+                    "bwd hd64 (H x 2)": lambda: A.attn_bwd(qkv, o64, lse64, do, H64)}
     else:
         o4, _ = A.attn_fwd(qkv, H, flags=4)
         o5, lse5 = A.attn_fwd(qkv, H, flags=16)
@@ -85,6 +94,10 @@ def main():
         fl = fwd_flops * (2.5 if k.startswith("bwd") else 1.0)
         print(f"{k:28s} median {v[len(v) // 2]:7.2f} us  min {v[0]:7.2f} us  ({fl / v[len(v) // 2] / 1e6:6.1f} TF/s)",
               flush=True)
+    if a.shape == "hd128":
+        med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+        print(f"hd128 / hd64 time per layer: fwd {med['fwd hd128'] / med['fwd hd64 (H x 2)']:.3f}  "
+              f"bwd {med['bwd hd128'] / med['bwd hd64 (H x 2)']:.3f}", flush=True)
 
 
 if __name__ == "__main__":

@@ -685,6 +685,9 @@ __global__ void __launch_bounds__(CH_THREADS) attn_fwd_chunk_kernel(const bf16* 
 // stays <= 2^FW_THR (exact in bf16 range, fp32 sums).  Block = 4 waves = 128 queries of one (b, h);
 // K/V stream through 2 LDS + 2 register stages (pipelined_tiles), one barrier per 64 keys; heavy
 // (late) query blocks first across the grid.
+// head_dim 128 (the only forward at that width): the same kernel with one 32-key block per softmax step
+// (`block` below) and the FwLds<128> pitches.  Compiled for gfx950: 198 VGPRs, 0 B scratch, 74 KB of LDS
+// -> 2 blocks per CU = 2 waves per SIMD (the O accumulator alone is 64 registers, so 3 do not fit).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -696,8 +699,13 @@ struct FwLds {
   // K image [key][KLD]: ds_read_b128 rows r = lane & 31 at a fixed 16-B chunk; row strides of 36 / 20
   // dwords put the 16 rows of every 16-lane read group on distinct 4-bank windows.  V image [key][VLD]:
   // ds_read_b64_tr_b16 reads 4 rows x 32 lanes; a row stride = 16 (mod 64) dwords makes them disjoint.
+  // head_dim 128: KLD = 136 bf16 = 68 dwords = 4 (mod 64), so row i of a 16-row read group starts at bank
+  // 4 i (16 distinct 4-bank windows); VLD = 160 bf16 = 80 dwords = 16 (mod 64), the smallest such pitch
+  // that holds a 128-wide row.  Stage = 64 x (136 + 160) x 2 B = 37 KB, two stages 74 KB per block, two
+  // blocks per CU 148 KB of the 160 KB.
   static constexpr int KLD = HD + 8;
-  static constexpr int VLD = HD == 32 ? 32 : 96;
+  static constexpr int VLD = HD == 32 ? 32 : HD == 64 ? 96 : 160;
+  static_assert(HD == 32 || HD == 64 || HD == 128, "pitches chosen per head_dim");
   static constexpr int STAGE = FW_KEYS * (KLD + VLD);
 };
 template <int HD>
@@ -823,6 +831,47 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
         for (int i = 0; i < HB; ++i) acc[i] = mfma32(vt_frag32(sV, L::VLD, 32 * k2 + 16 * s2, 32 * i, lane), pf, acc[i]);
       }
   };
+  // head_dim 128: one 32-key block per softmax step (the 64-key form above keeps 32 score registers and 16
+  // K fragments live beside the 64-register O accumulator and spills at 2 waves per SIMD), the diagonal mask
+  // under a wave-uniform branch inside ONE body.  Per block 8 QK^T + 8 PV MFMAs against 16 exponentials
+  // per lane: twice the MFMA work per softmax element of head_dim 64.
+  auto block = [&](const bf16* sK, const bf16* sV, int k2, int ks, bool diag) {
+    f32x16 sc = f32x16{};
+#pragma unroll
+    for (int c = 0; c < HC; ++c)
+      sc = mfma32(*(const bf16x8*)(sK + (k2 * 32 + r) * L::KLD + 16 * c + 8 * hh), qf[c], sc);
+    if (diag) {
+      const int lim = qlim - (ks + 4 * hh);  // keep key offset (i&3) + 8(i>>2) <= lim
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sc[i] = ((i & 3) + 8 * (i >> 2) <= lim) ? sc[i] : -INFINITY;
+    }
+    float mt = sc[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) mt = fmaxf(mt, sc[i]);
+    mt = pair_max32(mt) * cs;
+    if (__builtin_amdgcn_ballot_w64(mt > m + FW_THR) != 0) {
+      const float mn = mt > m + FW_THR ? mt : m;
+      const float alpha = fast_exp2(m - mn);
+      m = mn;
+      l *= alpha;
+#pragma unroll
+      for (int i = 0; i < HB; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][e] *= alpha;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float pv = fast_exp2(fmaf(sc[i], cs, -m));
+      sc[i] = pv;
+      l += pv;
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const bf16x8 pf = pack8(sc, s2);
+#pragma unroll
+      for (int i = 0; i < HB; ++i) acc[i] = mfma32(vt_frag32(sV, L::VLD, 32 * k2 + 16 * s2, 32 * i, lane), pf, acc[i]);
+    }
+  };
   const int nkt = (min(T, qblk * FW_QROWS + FW_QROWS) + FW_KEYS - 1) / FW_KEYS;
   RegStage<HD, FW_THREADS> rs;
   auto store = [&](int buf) {
@@ -843,8 +892,17 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
     const int kb = it * FW_KEYS;
     const bf16* sK = lds + (it & 1) * L::STAGE;
     if (kb <= q0 + 31 && q0 < T) {  // wave-uniform: else the whole tile lies past this wave's queries
-      if (kb + FW_KEYS - 1 > q0) tile(sK, sK + FW_KEYS * L::KLD, kb, std::true_type{});
-      else tile(sK, sK + FW_KEYS * L::KLD, kb, std::false_type{});
+      if constexpr (HD == 128) {
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const int ks = kb + 32 * k2;
+          if (ks > q0 + 31) break;  // wave-uniform: these 32 keys lie past every query of the wave
+          block(sK, sK + FW_KEYS * L::KLD, k2, ks, ks + 31 > q0);
+        }
+      } else {
+        if (kb + FW_KEYS - 1 > q0) tile(sK, sK + FW_KEYS * L::KLD, kb, std::true_type{});
+        else tile(sK, sK + FW_KEYS * L::KLD, kb, std::false_type{});
+      }
     }
     if (it + 1 < nkt) store((it + 1) & 1);
     __syncthreads();
@@ -1068,27 +1126,45 @@ __global__ void __launch_bounds__(FW_THREADS, WPS) attn_fwd5_kernel(const bf16* 
 // chunk c of row r at chunk position c ^ sw8(r), sw8(r) = ((r >> 1) & 1) << 2 | ((r >> 2) & 3).  The row
 // reads (rows lane & 31 of one chunk) then hit 16 distinct 4-bank windows per 16-lane read group, and a
 // transposed read (4 consecutive rows x 4 chunks per 32 lanes) all 64 banks once.
+// head_dim 128 (W = 128): 256-B rows span all 64 banks, so a chunk's position in its row IS its 4-bank
+// window, 16 chunks per row, chunk c of row r at c ^ sw16(r), sw16(r) = (r & 3) << 2 | ((r >> 2) & 3).
+// sw16 is a bijection of r & 15: the 16 rows of a row-read group sit on 16 distinct windows.  A transposed
+// read takes rows 4a + q (q = 0..3) x chunks 4b + j (j = 0..3): position ((b ^ q) << 2) | (j ^ (a & 3)),
+// 16 distinct windows = all 64 banks once.  Image = 64 x 128 x 2 B = 16 KB, stage (2 images + 2 vectors)
+// 32.5 KB, two stages 65 KB per block.
 __device__ __forceinline__ int sw8(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
+__device__ __forceinline__ int sw16(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
+template <int W>
+__device__ __forceinline__ int swz(int r) {
+  static_assert(W == 64 || W == 128, "swizzled image widths");
+  if constexpr (W == 64) return sw8(r);
+  else return sw16(r);
+}
+template <int W = 64>
 __device__ __forceinline__ bf16x8 sw_row(const bf16* t, int row, int ch) {
-  return *(const bf16x8*)(t + row * 64 + ((ch ^ sw8(row)) << 3));
+  DTC_ASSERT(row >= 0 && row < 64 && ch >= 0 && ch < W / 8);
+  return *(const bf16x8*)(t + row * W + ((ch ^ swz<W>(row)) << 3));
 }
 // A fragment of X^T (32 columns c0.. of the tile as rows, 16 tile rows k0.. as k, permuted order)
+template <int W = 64>
 __device__ __forceinline__ bf16x8 sw_tr(const bf16* t, int k0, int c0, int lane) {
   const int G = lane >> 4, qq = (lane >> 2) & 3, p = lane & 3;
   const int r0 = k0 + 4 * (G >> 1) + qq, r1 = r0 + 8, col = c0 + 16 * (G & 1) + 4 * p;
-  const bf16* p0 = t + r0 * 64 + (((col >> 3) ^ sw8(r0)) << 3) + (col & 7);
-  const bf16* p1 = t + r1 * 64 + (((col >> 3) ^ sw8(r1)) << 3) + (col & 7);
+  DTC_ASSERT(r0 >= 0 && r1 < 64 && col >= 0 && col + 4 <= W);
+  const bf16* p0 = t + r0 * W + (((col >> 3) ^ swz<W>(r0)) << 3) + (col & 7);
+  const bf16* p1 = t + r1 * W + (((col >> 3) ^ swz<W>(r1)) << 3) + (col & 7);
   s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((DTC_LDS s16x4*)(DTC_LDS void*)(p0));
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((DTC_LDS s16x4*)(DTC_LDS void*)(p1));
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-// Two [64][64] bf16 tiles (rows t0.., two operands, buffer-resource loads) + optionally two fp32 row vectors
-// [64] (lse, delta) for the swizzled images; ONE register set (T14: tile t+1 loaded before tile t's
+// Two [64][W] bf16 tiles (W = head_dim 64 or 128; rows t0.., two operands, buffer-resource loads) + optionally
+// two fp32 row vectors [64] (lse, delta) for the swizzled images; ONE register set (T14: tile t+1 loaded before tile t's
 // compute, written to the other LDS buffer after it), one barrier per tile.
-template <int NTH, bool VEC>
+template <int NTH, bool VEC, int W = 64>
 struct SwStage {
-  static constexpr int CPT = 64 * 8 / NTH;
+  static constexpr int CPR = W / 8;  // 16-B chunks per row
+  static constexpr int CPT = 64 * CPR / NTH;
   u32x4 x[CPT], y[CPT];
   f32x4 v;
   __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rx, long sx, __amdgpu_buffer_rsrc_t ry, long sy,
@@ -1096,7 +1172,7 @@ struct SwStage {
                                        int tid) {
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
-      const int c = tid + NTH * i, r = c >> 3, ch = c & 7;
+      const int c = tid + NTH * i, r = c / CPR, ch = c % CPR;
       x[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(((long)(t0 + r) * sx + 8 * ch) * 2), 0, 0));
       y[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(((long)(t0 + r) * sy + 8 * ch) * 2), 0, 0));
     }
@@ -1111,25 +1187,28 @@ struct SwStage {
   __device__ __forceinline__ void store(bf16* lx, bf16* ly, float* lv, int tid) const {
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
-      const int c = tid + NTH * i, r = c >> 3, ch = c & 7;
-      *(u32x4*)(lx + r * 64 + ((ch ^ sw8(r)) << 3)) = x[i];
-      *(u32x4*)(ly + r * 64 + ((ch ^ sw8(r)) << 3)) = y[i];
+      const int c = tid + NTH * i, r = c / CPR, ch = c % CPR;
+      DTC_ASSERT(r < 64 && (ch ^ swz<W>(r)) < CPR);
+      *(u32x4*)(lx + r * W + ((ch ^ swz<W>(r)) << 3)) = x[i];
+      *(u32x4*)(ly + r * W + ((ch ^ swz<W>(r)) << 3)) = y[i];
     }
     if (VEC && tid < 32) *(f32x4*)(lv + (tid < 16 ? 0 : 64) + 4 * (tid & 15)) = v;
   }
 };
-constexpr int SW_STAGE = 2 * 64 * 64 + 2 * 64 * 2;  // bf16 elements per stage (2 images + 2 fp32 vectors)
+template <int W>
+__host__ __device__ constexpr int sw_stage() { return 2 * 64 * W + 2 * 64 * 2; }  // bf16 per stage: 2 images + 2 fp32 vectors
+constexpr int SW_STAGE = sw_stage<64>();
 
 // body(sX, sY, sVec, it) over tiles t0_of(it)
-template <int NTH, bool VEC, typename T0, typename Body>
+template <int NTH, bool VEC, int W, typename T0, typename Body>
 __device__ __forceinline__ void sw_pipelined_tiles(int n, T0 t0_of, __amdgpu_buffer_rsrc_t rx, long sx,
                                                    __amdgpu_buffer_rsrc_t ry, long sy, const float* va,
                                                    const float* vb, int T, bf16* lds, int tid, Body body) {
   if (n <= 0) return;
-  auto X = [&](int k) { return lds + k * SW_STAGE; };
-  auto Y = [&](int k) { return lds + k * SW_STAGE + 64 * 64; };
-  auto Vv = [&](int k) { return (float*)(lds + k * SW_STAGE + 2 * 64 * 64); };
-  SwStage<NTH, VEC> st;
+  auto X = [&](int k) { return lds + k * sw_stage<W>(); };
+  auto Y = [&](int k) { return lds + k * sw_stage<W>() + 64 * W; };
+  auto Vv = [&](int k) { return (float*)(lds + k * sw_stage<W>() + 2 * 64 * W); };
+  SwStage<NTH, VEC, W> st;
   st.load(rx, sx, ry, sy, va, vb, t0_of(0), T, tid);
   st.store(X(0), Y(0), Vv(0), tid);
   __syncthreads();
@@ -1151,7 +1230,7 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
                                           const bf16* __restrict__ dout, const float* __restrict__ lse,
                                           float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int T, int H,
                                           float scale) {
-  static_assert(HD == 64, "swizzled 64-wide images");
+  static_assert(HD == 64 || HD == 128, "swizzled 64- / 128-wide images");
   constexpr int HC = HD / 16, HB = HD / 32;
   extern __shared__ __attribute__((aligned(16))) bf16 lds[];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
@@ -1196,10 +1275,24 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
   // (key <= q), whose rows are never written, and load as zeros (buffer range): the causal mask suffices.
   auto kblock = [&](const bf16* sK, const bf16* sV, int k2, int ks, bool diag) {
     f32x16 st = f32x16{}, dp = f32x16{};
+    int ln = lane;
+    if constexpr (HD == 128) {
+      // The 8 + 8 swizzled fragment addresses are loop invariants that hipcc hoists into ~30 registers, which
+      // spill beside the 64-register dQ accumulator and the stationary Q / dO fragments at 2 waves per SIMD.
+      // An opaque copy of the lane id makes them per-block values (one xor + one add each, under the MFMAs).
+      int rr = r;
+      asm volatile("" : "+v"(rr), "+v"(ln));
 #pragma unroll
-    for (int c = 0; c < HC; ++c) {
-      st = mfma32(sw_row(sK, 32 * k2 + r, 2 * c + hh), qf[c], st);
-      dp = mfma32(sw_row(sV, 32 * k2 + r, 2 * c + hh), df[c], dp);
+      for (int c = 0; c < HC; ++c) {
+        st = mfma32(sw_row<HD>(sK, 32 * k2 + rr, 2 * c + hh), qf[c], st);
+        dp = mfma32(sw_row<HD>(sV, 32 * k2 + rr, 2 * c + hh), df[c], dp);
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < HC; ++c) {
+        st = mfma32(sw_row<HD>(sK, 32 * k2 + r, 2 * c + hh), qf[c], st);
+        dp = mfma32(sw_row<HD>(sV, 32 * k2 + r, 2 * c + hh), df[c], dp);
+      }
     }
     const int lim = q - (ks + 4 * hh);  // register i holds key ks + 4h + (i & 3) + 8 (i >> 2)
 #pragma unroll
@@ -1214,7 +1307,8 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
     for (int s2 = 0; s2 < 2; ++s2) {
       const bf16x8 dsb = pack8(st, s2);
 #pragma unroll
-      for (int i = 0; i < HB; ++i) acc[i] = mfma32(sw_tr(sK, 32 * k2 + 16 * s2, 32 * i, lane), dsb, acc[i]);
+      for (int i = 0; i < HB; ++i)
+        acc[i] = mfma32(sw_tr<HD>(sK, 32 * k2 + 16 * s2, 32 * i, HD == 128 ? ln : lane), dsb, acc[i]);
     }
   };
   auto body = [&](const bf16* sK, const bf16* sV, const float*, int it) {
@@ -1228,8 +1322,8 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
     }
   };
   const int nkt = (min(T, qblk * FW_QROWS + FW_QROWS) + 63) / 64;
-  sw_pipelined_tiles<FW_THREADS, false>(nkt, [](int it) { return it * 64; }, rows_rsrc(Kb, ts, T, HD), ts,
-                                        rows_rsrc(Vb, ts, T, HD), ts, nullptr, nullptr, T, lds, tid, body);
+  sw_pipelined_tiles<FW_THREADS, false, HD>(nkt, [](int it) { return it * 64; }, rows_rsrc(Kb, ts, T, HD), ts,
+                                            rows_rsrc(Vb, ts, T, HD), ts, nullptr, nullptr, T, lds, tid, body);
   if (q < T) {
     bf16* pq = dqkv + ((long)b * T + q) * ts + (0 * H + h) * HD;
 #pragma unroll
@@ -1242,12 +1336,12 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
   }
 }
 
-template <int HD>
+template <int HD, bool DELTA_IN = false>
 __global__ void __launch_bounds__(FW_THREADS, 2) attn_bwd_dq32_kernel(
     const bf16* __restrict__ qkv, const bf16* __restrict__ o, const bf16* __restrict__ dout,
     const float* __restrict__ lse, float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int T, int H,
     float scale) {
-  dq32_body<HD, false>((int)blockIdx.x, qkv, o, dout, lse, delta, dqkv, B, T, H, scale);
+  dq32_body<HD, DELTA_IN>((int)blockIdx.x, qkv, o, dout, lse, delta, dqkv, B, T, H, scale);
 }
 
 // dK, dV: block = 4 waves = 128 keys of one (b, h); wave = 32 keys on the lane.  Per 32-query block:
@@ -1258,7 +1352,7 @@ template <int HD>
 __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                             const float* __restrict__ lse, const float* __restrict__ delta,
                                             bf16* __restrict__ dqkv, int B, int T, int H, float scale) {
-  static_assert(HD == 64, "swizzled 64-wide images");
+  static_assert(HD == 64 || HD == 128, "swizzled 64- / 128-wide images");
   constexpr int HC = HD / 16, HB = HD / 32;
   extern __shared__ __attribute__((aligned(16))) bf16 lds[];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
@@ -1294,8 +1388,8 @@ __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qk
     f32x16 sc = f32x16{}, dp = f32x16{};
 #pragma unroll
     for (int c = 0; c < HC; ++c) {
-      sc = mfma32(sw_row(sQ, 32 * k2 + r, 2 * c + hh), kf[c], sc);
-      dp = mfma32(sw_row(sD, 32 * k2 + r, 2 * c + hh), vf[c], dp);
+      sc = mfma32(sw_row<HD>(sQ, 32 * k2 + r, 2 * c + hh), kf[c], sc);
+      dp = mfma32(sw_row<HD>(sD, 32 * k2 + r, 2 * c + hh), vf[c], dp);
     }
     const int lim = key - (qs + 4 * hh);  // register 4 g4 + e holds query qs + 4h + 8 g4 + e
     f32x16 ds;
@@ -1321,8 +1415,8 @@ __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qk
       const bf16x8 pb = pack8(sc, s2), dsb = pack8(ds, s2);
 #pragma unroll
       for (int i = 0; i < HB; ++i) {
-        dv[i] = mfma32(sw_tr(sD, 32 * k2 + 16 * s2, 32 * i, lane), pb, dv[i]);
-        dk[i] = mfma32(sw_tr(sQ, 32 * k2 + 16 * s2, 32 * i, lane), dsb, dk[i]);
+        dv[i] = mfma32(sw_tr<HD>(sD, 32 * k2 + 16 * s2, 32 * i, lane), pb, dv[i]);
+        dk[i] = mfma32(sw_tr<HD>(sQ, 32 * k2 + 16 * s2, 32 * i, lane), dsb, dk[i]);
       }
     }
   };
@@ -1337,8 +1431,8 @@ __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qk
     }
   };
   const int nqt = (T - qt0 * 64 + 63) / 64;
-  sw_pipelined_tiles<FW_THREADS, true>(nqt, [qt0](int it) { return (qt0 + it) * 64; }, rows_rsrc(Qb, ts, T, HD), ts,
-                                       rows_rsrc(dOb, dts, T, HD), dts, lseb, delb, T, lds, tid, body);
+  sw_pipelined_tiles<FW_THREADS, true, HD>(nqt, [qt0](int it) { return (qt0 + it) * 64; }, rows_rsrc(Qb, ts, T, HD),
+                                           ts, rows_rsrc(dOb, dts, T, HD), dts, lseb, delb, T, lds, tid, body);
   if (key < T) {
     bf16* pk = dqkv + ((long)b * T + key) * ts + (1 * H + h) * HD;
     bf16* pv = dqkv + ((long)b * T + key) * ts + (2 * H + h) * HD;
@@ -1355,8 +1449,13 @@ __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qk
   }
 }
 
+// head_dim 128: the two accumulators are 128 registers and the stationary K / V fragments 64 more, past the
+// 256 a wave gets at 2 waves per SIMD, so that instantiation runs at 1 wave per SIMD (one block per CU)
+// with the whole 512-register file.  Compiled for gfx950: attn_bwd_dkdv32_kernel<128> 408 registers (248
+// VGPRs + 160 AGPRs), 0 B scratch; attn_bwd_dq32_kernel<128, true> 250 VGPRs, 0 B scratch, 2 waves per SIMD;
+// both 65 KB of LDS per block.
 template <int HD>
-__global__ void __launch_bounds__(FW_THREADS, 2) attn_bwd_dkdv32_kernel(
+__global__ void __launch_bounds__(FW_THREADS, HD == 128 ? 1 : 2) attn_bwd_dkdv32_kernel(
     const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int T, int H, float scale) {
   dkdv32_body<HD>((int)blockIdx.x, qkv, dout, lse, delta, dqkv, B, T, H, scale);
@@ -2121,6 +2220,16 @@ int dtc_attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, int 
     DTC_CHECK_LAUNCH();
     return 0;
   }
+  // head_dim 128: the 32-query-row kernel in the heavy-first block order (it takes no FwOrder, so there is
+  // no one-round precondition to meet); the A/B flags and DTC_ATTN_CHUNK pick head_dim 64 variants and are
+  // ignored here
+  if (HD == 128) {
+    allow_lds(attn_fwd32_kernel<128>, fw_lds_bytes<128>());
+    hipLaunchKernelGGL(attn_fwd32_kernel<128>, dim3(B * H * ((T + FW_QROWS - 1) / FW_QROWS)), dim3(FW_THREADS),
+                       fw_lds_bytes<128>(), st, qkv, o, lse, B, T, H, scale);
+    DTC_CHECK_LAUNCH();
+    return 0;
+  }
   // default at head_dim 64: the round-5 forward (2-deep K/V prefetch, V^T fragments ahead of the softmax, one
   // code path per tile; 26.6-26.9 vs 28.2-28.5 us per layer, profiles/r5_attention.md); flags bit 4 = the
   // round-4 kernel (A/B),
@@ -2201,6 +2310,19 @@ int dtc_attn_bwd(const bf16* qkv, const bf16* o, const float* lse, const bf16* d
     allow_lds(attn_bwd_res_kernel<32>, lds_b);
     hipLaunchKernelGGL(attn_bwd_res_kernel<32>, dim3(B * H * 4), dim3(RES_THREADS), lds_b, st, qkv, o, dout, lse,
                        dqkv, B, T, H, scale);
+  } else if (HD == 128) {
+    // head_dim 128: delta pass, then the 32x32x16 dK/dV (1 wave per SIMD) and dQ (2 per SIMD) kernels as two
+    // launches (their register budgets differ, so they do not share the merged kernel); flags ignored
+    constexpr int lb = 2 * sw_stage<128>() * 2;
+    static_assert(2 * lb <= LDS_MAX, "two dQ blocks per CU");
+    allow_lds(attn_bwd_dkdv32_kernel<128>, lb);
+    allow_lds((attn_bwd_dq32_kernel<128, true>), lb);
+    const dim3 g32(B * H * ((T + FW_QROWS - 1) / FW_QROWS));
+    launch_attn_delta<128>(o, dout, ws, B, T, H, st);
+    hipLaunchKernelGGL(attn_bwd_dkdv32_kernel<128>, g32, dim3(FW_THREADS), lb, st, qkv, dout, lse, ws, dqkv, B, T, H,
+                       scale);
+    hipLaunchKernelGGL((attn_bwd_dq32_kernel<128, true>), g32, dim3(FW_THREADS), lb, st, qkv, o, dout, lse, ws, dqkv,
+                       B, T, H, scale);
   } else if (attn_chunk_enabled() && (HD == 32 || HD == 64)) {
     const dim3 g(B * H * ((T + CH_QROWS - 1) / CH_QROWS)), gk(B * H * ((T + CHB_KROWS - 1) / CHB_KROWS));
     if (HD == 64 && !(flags & 4)) {

@@ -21,6 +21,9 @@
 // Deterministic: no atomics (separate dK/dV and dQ kernels, each output written by one wave).
 // Softmax runs in the log2 domain (scores pre-multiplied by scale*log2(e), v_exp_f32): ~1 ulp per
 // exponential, i.e. ~1e-6 relative on P at the score ranges here (tests: 1e-5 of the float64 result).
+// head_dim 32, 64 and 128.  At 128 (AF<128>: 32-row stages in dynamic LDS) compiled for gfx950: forward 234
+// VGPRs, 66 KB LDS, 2 waves per SIMD; dK/dV 472 registers (256 VGPRs + 216 AGPRs) and dQ 362 (256 + 106), 67 /
+// 66 KB LDS, 1 wave per SIMD; 0 B scratch in all three.
 #include "common.h"
 
 namespace {
@@ -30,7 +33,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int AW = 4;           // waves per block
 constexpr int AT = AW * 64;     // threads
 constexpr int QB = 32 * AW;     // rows (queries or keys) owned by one block
-constexpr int ST = 64;          // streamed rows per LDS stage (2 sub-tiles of 32)
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -39,6 +41,15 @@ __device__ __forceinline__ int rowmap(int r, int half) { return (r & 3) + 8 * (r
 
 template <int HD>
 struct AF {
+  // streamed rows per LDS stage (sub-tiles of 32).  head_dim 128: 32 rows, so a [K | V] stage pair is
+  // 2 x 2 x 32 x 132 x 4 B = 66 KB (135 KB at 64 rows: one block per CU) and a thread stages 4 + 4 float4
+  // instead of 8 + 8 beside the 64-register stationary operand and the 64-register accumulator.
+  static constexpr int ST = HD == 128 ? 32 : 64;
+  static constexpr int NSUB = ST / 32;
+  // blocks per CU promised to the compiler by the backward kernels: head_dim 128 keeps two stationary
+  // operands (128 registers) and, in dK/dV, two accumulators (128 more): past the 256 registers of 2
+  // waves per SIMD, so those run 1 wave per SIMD with the whole 512-register file and no scratch.
+  static constexpr int BWD_WPS = HD == 128 ? 1 : 2;
   static constexpr int LD = HD + 4;      // padded LDS row pitch (floats)
   static constexpr int NC = HD / 8;      // 8-wide d chunks = 4 permuted MFMA k-steps each
   static constexpr int DT = HD / 32;     // 32-wide d tiles of an O / dQ / dK / dV accumulator
@@ -46,6 +57,22 @@ struct AF {
   static constexpr int CH = ST * HD / 4; // float4 chunks per streamed tile
   static constexpr int PT = CH / AT;     // per thread
   static_assert(CH % AT == 0, "");
+  static constexpr int FWD_LDS = 2 * 2 * TILE;              // floats: [buf][K | V] (forward, dQ)
+  static constexpr int DKDV_LDS = 2 * (2 * TILE + 2 * ST);  // floats: [buf][Q | dO | lse | delta]
+
+  // LDS base: the static array of head_dim 32 / 64 as before; dynamic LDS (opted into with
+  // hipFuncSetAttribute at launch) at head_dim 128
+  static constexpr bool DYN_LDS = HD > 64;
+  template <int N>
+  __device__ __forceinline__ static float* lds_base() {
+    if constexpr (!DYN_LDS) {
+      __shared__ __attribute__((aligned(16))) float smem[N];
+      return smem;
+    } else {
+      extern __shared__ __attribute__((aligned(16))) float dyn_smem[];
+      return dyn_smem;
+    }
+  }
 
   // global row t of a [*, row_stride] tensor, columns [col0, col0 + HD)
   __device__ __forceinline__ static void load(f32x4 (&reg)[PT], const float* base, long row_stride, int t0, int T,
@@ -122,7 +149,8 @@ struct AttnFArgs {
 template <int HD>
 __global__ void __launch_bounds__(AT, 2) attn_f32_fwd_kernel(AttnFArgs a) {
   using F = AF<HD>;
-  __shared__ __attribute__((aligned(16))) float smem[2 * 2 * F::TILE];  // [buf][K | V]
+  constexpr int ST = F::ST;
+  float* const smem = F::template lds_base<F::FWD_LDS>();  // [buf][K | V]
   const int nqb = (a.T + QB - 1) / QB;
   const int bh = blockIdx.x / nqb, qb = nqb - 1 - blockIdx.x % nqb;  // longest (last) query blocks first
   const int b = bh / a.H, h = bh % a.H;
@@ -160,7 +188,7 @@ __global__ void __launch_bounds__(AT, 2) attn_f32_fwd_kernel(AttnFArgs a) {
       F::load(rv, vg, rs, (st + 1) * ST, a.T, tid);
     }
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
+    for (int sub = 0; sub < F::NSUB; ++sub) {
       const int kb = st * ST + sub * 32;
       if (kb > qw + 31) continue;  // wave-uniform: the whole sub-tile is above this wave's diagonal
       f32x16 s = F::template dot<true>(sK + sub * 32 * F::LD, qreg, l32, half);  // S^T[key][q]
@@ -230,9 +258,10 @@ __global__ void __launch_bounds__(256) attn_f32_delta_kernel(const float* __rest
 // dK, dV for a block of QB keys (wave w owns keys k0 + 32w ..), streaming Q / dO stages from the
 // diagonal down.  Orientation S[q][key]: key on the lane, 16 query rows in registers.
 template <int HD>
-__global__ void __launch_bounds__(AT, 2) attn_f32_dkdv_kernel(AttnFArgs a) {
+__global__ void __launch_bounds__(AT, AF<HD>::BWD_WPS) attn_f32_dkdv_kernel(AttnFArgs a) {
   using F = AF<HD>;
-  __shared__ __attribute__((aligned(16))) float smem[2 * (2 * F::TILE + 2 * ST)];  // [buf][Q | dO | lse | delta]
+  constexpr int ST = F::ST;
+  float* const smem = F::template lds_base<F::DKDV_LDS>();  // [buf][Q | dO | lse | delta]
   constexpr int BUF = 2 * F::TILE + 2 * ST;
   const int nkb = (a.T + QB - 1) / QB;
   const int bh = blockIdx.x / nkb, kbk = blockIdx.x % nkb;  // first key blocks have the most queries
@@ -289,7 +318,7 @@ __global__ void __launch_bounds__(AT, 2) attn_f32_dkdv_kernel(AttnFArgs a) {
     const bool more = s + 1 < nst;
     if (more) ld_stage(s + 1);
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
+    for (int sub = 0; sub < F::NSUB; ++sub) {
       const int qs = s * ST + sub * 32;
       if (qs + 31 < kw) continue;  // wave-uniform: every query of the sub-tile precedes this wave's keys
       const float* Qr = sQ + sub * 32 * F::LD;
@@ -327,9 +356,10 @@ __global__ void __launch_bounds__(AT, 2) attn_f32_dkdv_kernel(AttnFArgs a) {
 
 // dQ for a block of QB queries, streaming K / V stages up to the diagonal.  Orientation S^T[key][q].
 template <int HD>
-__global__ void __launch_bounds__(AT, 2) attn_f32_dq_kernel(AttnFArgs a) {
+__global__ void __launch_bounds__(AT, AF<HD>::BWD_WPS) attn_f32_dq_kernel(AttnFArgs a) {
   using F = AF<HD>;
-  __shared__ __attribute__((aligned(16))) float smem[2 * 2 * F::TILE];  // [buf][K | V]
+  constexpr int ST = F::ST;
+  float* const smem = F::template lds_base<F::FWD_LDS>();  // [buf][K | V]
   const int nqb = (a.T + QB - 1) / QB;
   const int bh = blockIdx.x / nqb, qb = nqb - 1 - blockIdx.x % nqb;
   const int b = bh / a.H, h = bh % a.H;
@@ -369,7 +399,7 @@ __global__ void __launch_bounds__(AT, 2) attn_f32_dq_kernel(AttnFArgs a) {
       F::load(rv, vg, rs, (st + 1) * ST, a.T, tid);
     }
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
+    for (int sub = 0; sub < F::NSUB; ++sub) {
       const int kb = st * ST + sub * 32;
       if (kb > qw + 31) continue;
       const float* Kr = sK + sub * 32 * F::LD;
@@ -402,10 +432,20 @@ __global__ void __launch_bounds__(AT, 2) attn_f32_dq_kernel(AttnFArgs a) {
   }
 }
 
+// dynamic LDS bytes of a kernel whose AF::lds_base<N> is the dynamic array (0: it is static); more than
+// 64 KB of dynamic LDS must be opted into per kernel
+template <int HD, typename K>
+int dyn_lds(K kernel, int floats) {
+  if (!AF<HD>::DYN_LDS) return 0;
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, floats * 4);
+  return floats * 4;
+}
+
 template <int HD>
 int launch_fwd(const AttnFArgs& a, hipStream_t st) {
   const int blocks = a.B * a.H * ((a.T + QB - 1) / QB);
-  hipLaunchKernelGGL(attn_f32_fwd_kernel<HD>, dim3(blocks), dim3(AT), 0, st, a);
+  const int dyn = dyn_lds<HD>(attn_f32_fwd_kernel<HD>, AF<HD>::FWD_LDS);
+  hipLaunchKernelGGL(attn_f32_fwd_kernel<HD>, dim3(blocks), dim3(AT), dyn, st, a);
   DTC_CHECK_LAUNCH();
   return 0;
 }
@@ -413,9 +453,11 @@ int launch_fwd(const AttnFArgs& a, hipStream_t st) {
 template <int HD>
 int launch_bwd(const AttnFArgs& a, hipStream_t st) {
   const int blocks = a.B * a.H * ((a.T + QB - 1) / QB);
-  hipLaunchKernelGGL(attn_f32_dkdv_kernel<HD>, dim3(blocks), dim3(AT), 0, st, a);
+  const int dyn_k = dyn_lds<HD>(attn_f32_dkdv_kernel<HD>, AF<HD>::DKDV_LDS);
+  hipLaunchKernelGGL(attn_f32_dkdv_kernel<HD>, dim3(blocks), dim3(AT), dyn_k, st, a);
   DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_f32_dq_kernel<HD>, dim3(blocks), dim3(AT), 0, st, a);
+  const int dyn_q = dyn_lds<HD>(attn_f32_dq_kernel<HD>, AF<HD>::FWD_LDS);
+  hipLaunchKernelGGL(attn_f32_dq_kernel<HD>, dim3(blocks), dim3(AT), dyn_q, st, a);
   DTC_CHECK_LAUNCH();
   return 0;
 }
@@ -431,6 +473,7 @@ int dtc_attn_f32_fwd(const float* qkv, float* o, float* lse, int B, int T, int H
   a.qkv = qkv; a.out = o; a.lse_out = lse; a.B = B; a.T = T; a.H = H; a.scale = scale;
   if (HD == 32) return launch_fwd<32>(a, st);
   if (HD == 64) return launch_fwd<64>(a, st);
+  if (HD == 128) return launch_fwd<128>(a, st);
   return 4101;
 }
 
@@ -449,6 +492,7 @@ int dtc_attn_f32_bwd(const float* qkv, const float* o, const float* lse, const f
   a.B = B; a.T = T; a.H = H; a.scale = scale;
   if (HD == 32) return launch_bwd<32>(a, st);
   if (HD == 64) return launch_bwd<64>(a, st);
+  if (HD == 128) return launch_bwd<128>(a, st);
   return 4101;
 }
 

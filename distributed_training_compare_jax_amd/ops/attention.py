@@ -5,7 +5,9 @@ additive ``-1e9`` causal mask (``model/GPTModel.py:50-51``) and the full ``[B,H,
 score tensor materialised.  Here the mask is an in-kernel predicate (``-1e9`` then ``exp``
 is exactly 0 in fp32, so the semantics are identical) and the scores never leave the chip:
 ``csrc/attention.hip`` is a flash-style kernel (online softmax, LSE saved for backward,
-P recomputed in backward) on ``mfma_f32_16x16x32_bf16`` with head_dim = 32 = one MFMA K.
+P recomputed in backward) for head_dim 32, 64 and 128: ``mfma_f32_16x16x32_bf16`` kernels resident in LDS
+at head_dim 32 (= one MFMA K), ``mfma_f32_32x32x16_bf16`` kernels with 32 queries or keys per wave at head_dim
+64 and 128.  Any other head_dim raises ``NotImplementedError`` before anything is launched.
 fp32 tensors (the exact-fp32 parity mode) run ``csrc/attention_f32.hip``: the same algorithm on
 ``v_mfma_f32_32x32x2_f32`` (exact f32), again with no ``[B,H,T,T]`` tensor anywhere.
 
@@ -27,7 +29,8 @@ def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags:
     ``dtc_attn_fwd``): bit 0 the resident kernel's plain wave → query-group order; bit 2 the 16-row chunked
     kernel; bit 4 the round-4 32-row kernel; bit 5 the round-5 forward at 2 waves per SIMD (the default
     runs it at 3); bit 6 its heavy-first block order (the default assigns query blocks to CU slots
-    longest-processing-time-first)."""
+    longest-processing-time-first).  Every bit picks a head_dim 64 (bit 0: head_dim 32) variant; head_dim 128
+    has one forward kernel and ignores ``flags``."""
     B, T, C3 = qkv.shape
     hd = C3 // (3 * n_heads)
     scale = scale if scale is not None else hd ** -0.5
@@ -41,8 +44,8 @@ def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags:
         o = torch.einsum("bhts,bshd->bthd", p, v).reshape(B, T, n_heads * hd)
         return o.to(qkv.dtype), lse
     assert qkv.dtype in (torch.bfloat16, torch.float32) and qkv.is_contiguous()
-    if hd != 32 and hd != 64:
-        raise NotImplementedError(f"attention kernel supports head_dim 32/64, got {hd}")
+    if hd not in (32, 64, 128):
+        raise NotImplementedError(f"attention kernel supports head_dim 32/64/128, got {hd}")
     o = torch.empty(B, T, n_heads * hd, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(B, n_heads, T, dtype=torch.float32, device=qkv.device)
     if qkv.dtype == torch.float32:
@@ -57,7 +60,8 @@ def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags:
 def attn_bwd(qkv: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor, n_heads: int,
              scale: float | None = None, flags: int = 0) -> torch.Tensor:
     """Returns dqkv [B,T,3*H*hd] (same dtype as qkv).  ``flags`` bit 0 forces the two-round resident
-    kernels instead of the fused single-round one (A/B and tests)."""
+    kernels instead of the fused single-round one (A/B and tests).  head_dim 128 has one backward path
+    (delta pass, dK/dV kernel, dQ kernel) and ignores ``flags``."""
     B, T, C3 = qkv.shape
     hd = C3 // (3 * n_heads)
     scale = scale if scale is not None else hd ** -0.5
