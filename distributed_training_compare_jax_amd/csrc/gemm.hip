@@ -2625,6 +2625,30 @@ struct Plan {
   int bm, bn, bk, split;
 };
 
+// Record of the last launch: which kernel family ran, on what tile, with what split-K and sub-variant.
+// Written by the launch sites themselves (never recomputed from the plan functions, so it cannot drift
+// from what was launched); read by dtc_gemm_last_launch (tests assert the family a shape lands on).
+enum {
+  FAM_NONE = 0,
+  FAM_REG = 1,       // gemm_kernel, register-staged; sub = BK (32 / 64)
+  FAM_DMA64 = 2,     // gemm_dma_kernel 64^2 NT; sub = stages
+  FAM_DMAW = 3,      // gemm_dmaw_kernel; sub = stages, aux = wave grid WGM * 10 + WGN
+  FAM_BIG = 4,       // gemm8p_kernel; sub = CB (4 = 256^2, 3 = the 256 x 192 plan)
+  FAM_R8 = 5,        // gemm8r_kernel; sub = CB2, aux = n_split (columns on 256^2 tiles)
+  FAM_N8 = 6,        // gemm8n_kernel; sub = CB
+  FAM_PAIR = 7,      // gemm_pair_kernel; bm / bn = dgrad / weight-gradient tile, split = the weight gradient's
+  FAM_WGROUP = 8,    // gemm8p_group_kernel; split = tail split, sub = tail tiles, aux = all tiles
+  FAM_CE_DGRAD = 9,  // ce_dgrad256_kernel
+  FAM_LN = 10,       // gemm_dmaw_kernel with a LayerNorm epilogue; sub = 1 backward, 0 forward
+};
+struct LastLaunch {
+  int family, bm, bn, split, sub, aux, layout, epi;
+};
+static LastLaunch g_last{};
+inline void note_launch(int family, int bm, int bn, int split, int sub, int aux, int layout, int epi) {
+  g_last = LastLaunch{family, bm, bn, split, sub, aux, layout, epi};
+}
+
 // LDS-DMA variant of the 64x64 forward-layout tiles (measured fc2/out_proj fwd 22 -> 18.6 us; the
 // dgrad / wgrad layouts and the 128x128 tiles measured slower or equal on it and stay register-staged).
 // DTC_GEMM_DMA=0: register-staged everywhere (diagnostic)
@@ -2736,6 +2760,7 @@ int launch_t(const GemmArgs& a, const Plan& p, hipStream_t st) {
                          a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm, p.split, kps,
                          (float*)a.workspace, e);
       DTC_CHECK_LAUNCH();
+      note_launch(FAM_DMA64, BM, BN, p.split, 4, 0, a.layout, EPI);
       if (p.split > 1 && !a.defer_reduce) {
         long MN = (long)a.M * a.N;
         int blocks = (int)((MN / 4 + 255) / 256);
@@ -2746,15 +2771,17 @@ int launch_t(const GemmArgs& a, const Plan& p, hipStream_t st) {
       return 0;
     }
   }
-  if (p.bk == 32)
+  if (p.bk == 32) {
     hipLaunchKernelGGL((gemm_kernel<BM, BN, 32, AK, BKM, EPI, OUTF32>), grid, dim3(NT), 0, st, (const bf16*)a.A, a.lda,
                        ab, (const bf16*)a.B, a.ldb, bb, a.M, a.N, a.K, tiles_m, tiles_n, gm, p.split, kps,
                        (float*)a.workspace, e);
-  else if (p.bk == 64)
+    note_launch(FAM_REG, BM, BN, p.split, 32, 0, a.layout, EPI);
+  } else if (p.bk == 64) {
     hipLaunchKernelGGL((gemm_kernel<BM, BN, 64, AK, BKM, EPI, OUTF32>), grid, dim3(NT), 0, st, (const bf16*)a.A, a.lda,
                        ab, (const bf16*)a.B, a.ldb, bb, a.M, a.N, a.K, tiles_m, tiles_n, gm, p.split, kps,
                        (float*)a.workspace, e);
-  else
+    note_launch(FAM_REG, BM, BN, p.split, 64, 0, a.layout, EPI);
+  } else
     return 1007;
   DTC_CHECK_LAUNCH();
   if (p.split > 1 && !a.defer_reduce) {
@@ -2860,6 +2887,7 @@ int launch_big(const GemmArgs& a, int split, hipStream_t st) {
                          (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tn3, gm3, split,
                          kps, (float*)a.workspace, e);
       DTC_CHECK_LAUNCH();
+      note_launch(FAM_BIG, BIG, 192, split, 3, 0, a.layout, EPI);
       done = true;
     }
   }
@@ -2868,6 +2896,7 @@ int launch_big(const GemmArgs& a, int split, hipStream_t st) {
                        (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm, split,
                        kps, (float*)a.workspace, e);
     DTC_CHECK_LAUNCH();
+    note_launch(FAM_BIG, BIG, BIG, split, 4, 0, a.layout, EPI);
   }
   if (split > 1 && !a.defer_reduce) {
     long MN = (long)a.M * a.N;
@@ -2942,6 +2971,7 @@ int launch_r8_cb(const GemmArgs& a, const R8Plan& pl, hipStream_t st) {
   const int grid = r.nb1 + r.tm * r.tn2;
   hipLaunchKernelGGL((gemm8r_kernel<AK, BKM, EPI, OUTF32, CB2>), dim3(grid), dim3(NT2), 0, st, r, e);
   DTC_CHECK_LAUNCH();
+  note_launch(FAM_R8, BIG, 64 * CB2, 1, CB2, pl.n_split, a.layout, EPI);
   return 0;
 }
 
@@ -2997,6 +3027,7 @@ int launch_n8(const GemmArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((gemm8n_kernel<CB, NS, AK, BKM, EPI, OUTF32>), dim3(grid), dim3(NT2), 0, st,
                      (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm, e);
   DTC_CHECK_LAUNCH();
+  note_launch(FAM_N8, 128, 64 * CB, 1, CB, 0, a.layout, EPI);
   return 0;
 }
 
@@ -3036,6 +3067,7 @@ int launch_pair_t(const GemmArgs& a1, const Plan& p1, const GemmArgs& a2, const 
   hipLaunchKernelGGL((gemm_pair_kernel<C1, C2>), dim3(g1.nblocks + g2.nblocks), dim3(NT), 0, st, g1, g2,
                      second_first);
   DTC_CHECK_LAUNCH();
+  note_launch(FAM_PAIR, BM1, BM2, p2.split, second_first, 0, a1.layout, a1.epi);
   return 0;
 }
 
@@ -3135,6 +3167,7 @@ int launch_w(const GemmArgs& a, int split, hipStream_t st) {
                      dim3(64 * WGM * WGN), 0, st, (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m,
                      tiles_n, gm, split, kps, (float*)a.workspace, e);
   DTC_CHECK_LAUNCH();
+  note_launch(FAM_DMAW, BM, BN, split, NS, WGM * 10 + WGN, a.layout, EPI);
   if (split > 1 && !a.defer_reduce) {
     long MN = (long)a.M * a.N;
     hipLaunchKernelGGL(splitk_reduce, dim3((int)((MN / 4 + 255) / 256)), dim3(256), 0, st, (const float*)a.workspace, split,
@@ -3219,6 +3252,7 @@ int dtc_ce_dgrad(const bf16* logits, long ldl, const float* lse, const int* labe
   a.kps = big_kps(K, split);
   hipLaunchKernelGGL(ce_dgrad256_kernel, dim3(ntiles * split), dim3(NT2), 0, st, a);
   DTC_CHECK_LAUNCH();
+  note_launch(FAM_CE_DGRAD, BIG, BIG, split, 0, 0, 1, EPI_STORE);
   const long MN = (long)M * N;
   hipLaunchKernelGGL(splitk_reduce, dim3((int)((MN / 4 + 255) / 256)), dim3(256), 0, st, (const float*)ws, split, MN,
                      dx, (long)N, N, 0.f);
@@ -3248,6 +3282,7 @@ int dtc_gemm_ln(const LnArgs* a, hipStream_t st) {
                        (const bf16*)a->A, a->lda, (const bf16*)a->B, a->ldb, a->M, a->N, a->K, tiles_m, tiles_n, tiles_m,
                        1, a->K, nullptr, e);
   DTC_CHECK_LAUNCH();
+  note_launch(FAM_LN, 128, 64, 1, a->bwd ? 1 : 0, 0, 0, a->bwd ? EPI_LN_BWD : EPI_RESID_LN);
   return 0;
 }
 
@@ -3361,6 +3396,7 @@ int dtc_wgrad_group(const WgBatch* in, hipStream_t st) {
   if (!tail) b.tail_slab = nullptr;
   hipLaunchKernelGGL(gemm8p_group_kernel, dim3(t - tail + tail * b.tail_split), dim3(NT2), 0, st, b);
   DTC_CHECK_LAUNCH();
+  note_launch(FAM_WGROUP, BIG, BIG, b.tail_split, tail, t, 2, EPI_STORE);
   if (tail) {
     hipLaunchKernelGGL(wg_tail_reduce, dim3(tail * 8), dim3(WGT_THREADS), 0, st, b);
     DTC_CHECK_LAUNCH();
@@ -3379,6 +3415,14 @@ int dtc_gemm_set_r8_ilv(int on) {
   const int old = g_r8_ilv;
   g_r8_ilv = on;
   return old;
+}
+
+// the record of the last launch (LastLaunch): out[8] = family, BM, BN, split-K, sub-variant, aux, layout, epilogue
+int dtc_gemm_last_launch(int* out) {
+  const LastLaunch l = g_last;
+  out[0] = l.family; out[1] = l.bm; out[2] = l.bn; out[3] = l.split;
+  out[4] = l.sub; out[5] = l.aux; out[6] = l.layout; out[7] = l.epi;
+  return 0;
 }
 
 int dtc_gemm(const GemmArgs* a, hipStream_t st) {
@@ -3426,6 +3470,8 @@ int dtc_gemm(const GemmArgs* a, hipStream_t st) {
   if (a->layout == 0) {
     Plan p = make_plan(a->M, a->N, a->K, 0);
     const int bs0 = big_split(0, a->M, a->N, a->K);
+    // the split-K slabs hold bare accumulators and splitk_reduce knows no bias: refuse it, do not drop it
+    if (bs0 > 1 && epi == EPI_STORE && f32 && a->bias) return 1010;
     if (bs0 > 1 && epi == EPI_STORE && f32) return launch_big<true, true, EPI_STORE, true>(*a, bs0, st);
     if (bs0 == 1) {
       if (epi == EPI_LMHEAD) return launch_big<true, true, EPI_LMHEAD, false>(*a, 1, st);

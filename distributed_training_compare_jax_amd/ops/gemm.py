@@ -23,6 +23,7 @@ oracle / gloo path).
 
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 from typing import Optional
@@ -119,6 +120,27 @@ def _gemm_args(layout: int, M: int, N_: int, K: int, a, lda: int, b, ldb: int, c
         workspace=N.ptr(ws), ws_bytes=0 if ws is None else ws.numel(), split_k=0, defer_reduce=defer_reduce,
         colsum=N.ptr(colsum))
     return args
+
+
+# kernel families of csrc/gemm.hip (enum FAM_* there, keep in sync)
+FAMILIES = ("none", "gemm_kernel", "gemm_dma_kernel", "gemm_dmaw_kernel", "gemm8p_kernel", "gemm8r_kernel",
+            "gemm8n_kernel", "gemm_pair_kernel", "gemm8p_group_kernel", "ce_dgrad256_kernel", "gemm_dmaw_kernel_ln")
+
+LastLaunch = collections.namedtuple("LastLaunch", "family bm bn split_k sub aux layout epi")
+
+
+def last_launch() -> LastLaunch:
+    """What the last bf16 GEMM launch of this process ran, as recorded by the launch site itself
+    (csrc/gemm.hip ``note_launch``): ``family`` (one of :data:`FAMILIES`), the tile ``bm`` x ``bn``, the
+    split-K factor and the sub-variant ``sub``: BK for ``gemm_kernel``, the stage count for the DMA kernels
+    (``aux`` = wave grid WGM * 10 + WGN), CB for ``gemm8p_kernel`` (3 = the 256 x 192 plan) / ``gemm8n_kernel``,
+    CB2 for ``gemm8r_kernel`` (``aux`` = columns on 256^2 tiles); ``gemm_pair_kernel``: ``bm`` / ``bn`` are the
+    dgrad / weight-gradient tiles and ``split_k`` the weight gradient's; ``gemm8p_group_kernel``: ``split_k`` =
+    tail split, ``sub`` = tail tiles, ``aux`` = all tiles.  Tests assert it; nothing on the hot path reads it."""
+    out = (ctypes.c_int * 8)()
+    N.check(N.lib().dtc_gemm_last_launch(out), "dtc_gemm_last_launch")
+    v = list(out)
+    return LastLaunch(FAMILIES[v[0]], *v[1:])
 
 
 def _check2d(t: torch.Tensor, name: str):

@@ -30,8 +30,15 @@ def _close(a, b, rtol, name):
 def n8(cuda):
     L = N.lib()
     old = L.dtc_gemm_set_n8(7)  # every whole-round shape (the default takes one-round shapes)
+    old_mink = L.dtc_gemm_set_n8_mink(768)  # also the one-round K = 768 shapes (out_proj; default 1024)
     yield L
+    L.dtc_gemm_set_n8_mink(old_mink)
     L.dtc_gemm_set_n8(old)
+
+
+def _ran_n8(cb=None):
+    ll = G.last_launch()
+    assert ll.family == "gemm8n_kernel" and (cb is None or ll.sub == cb), ll
 
 
 # (M, N, K): GPT-2 small qkv / out_proj / fc1 / fc2 (8192 tokens), ragged M (8100 -> 64 M-tiles),
@@ -45,19 +52,26 @@ def test_n8_forward_epilogues(n8, M, Nn, K):
     x, w = _r(M, K, seed=1), _r(Nn, K, scale=0.05, seed=2)
     b = _r(Nn, seed=3, dtype=torch.float32)
     ref = x.float() @ w.float().t() + b
+    cb = 3 if Nn % 192 == 0 else 4
     y = G.linear(x, w, b)
+    _ran_n8(cb)
     _close(y, ref, 1e-2, "store_bf16")
     res = _r(M, Nn, seed=4, dtype=torch.float32)
     yr = G.linear_resid(x, w, b, res)
+    _ran_n8(cb)
     _close(yr, ref + res, 2e-3, "resid_f32")
     u, g = G.linear_gelu(x, w, b)
+    _ran_n8(cb)
     _close(u, G.gelu_tanh_grad(ref), 1e-2, "gelu_grad")
     _close(g, G.gelu_tanh(ref), 1e-2, "gelu")
     # NT dgrad on a transposed weight (fp32 out), as the fc1 / qkv backward runs it
-    _close(G.linear(x, w, out_dtype=torch.float32), ref - b, 2e-3, "nt_f32")
+    yf = G.linear(x, w, out_dtype=torch.float32)
+    _ran_n8(cb)
+    _close(yf, ref - b, 2e-3, "nt_f32")
     # the 128^2 / 256^2 kernels agree closely (same bf16 operands, fp32 accumulation, other k order)
     n8.dtc_gemm_set_n8(0)
     yr0 = G.linear_resid(x, w, b, res)
+    assert G.last_launch().family != "gemm8n_kernel", G.last_launch()
     n8.dtc_gemm_set_n8(7)
     _close(yr, yr0, 1e-4, "n8_vs_tiled")
     assert torch.equal(yr, G.linear_resid(x, w, b, res)), "not run-to-run deterministic"
@@ -71,12 +85,15 @@ def test_n8_dgrad(n8, M, Nn, K):
     """dX[M, K] = dY[M, Nn] . W[Nn, K] (layout nn: W is the MN-major operand), plain and dGELU."""
     dy, w = _r(M, Nn, seed=5), _r(Nn, K, scale=0.05, seed=6)
     ref = dy.float() @ w.float()
-    _close(G.matmul_nn(dy, w), ref, 2e-3, "nn_f32")
-    _close(G.matmul_nn(dy, w, out_dtype=torch.bfloat16), ref, 1e-2, "nn_bf16")
     u = _r(M, K, seed=7)
-    _close(G.matmul_nn_dgelu(dy, w, u), ref * u.float(), 1e-2, "dgelu")
-    # fused with the GELU backward as NT on W^T
-    _close(G.matmul_nt_dgelu(dy, w.t().contiguous(), u), ref * u.float(), 1e-2, "nt_dgelu")
+    # the last: fused with the GELU backward as NT on W^T
+    for name, rtol, want, fn in (("nn_f32", 2e-3, ref, lambda: G.matmul_nn(dy, w)),
+                                 ("nn_bf16", 1e-2, ref, lambda: G.matmul_nn(dy, w, out_dtype=torch.bfloat16)),
+                                 ("dgelu", 1e-2, ref * u.float(), lambda: G.matmul_nn_dgelu(dy, w, u)),
+                                 ("nt_dgelu", 1e-2, ref * u.float(), lambda: G.matmul_nt_dgelu(dy, w.t().contiguous(), u))):
+        out = fn()
+        _ran_n8()
+        _close(out, want, rtol, name)
 
 
 def test_n8_selection(n8):
@@ -91,6 +108,7 @@ def test_n8_selection(n8):
     red = GradReducer(torch.device("cuda"), arena_mb=64)
     dw = torch.zeros(Nn, K, device="cuda")
     dx = G.linear_backward(dy, w, x, dw, red=red)
+    assert G.last_launch().family not in ("gemm_pair_kernel", "gemm8n_kernel"), G.last_launch()  # the weight gradient's own launch
     red.flush_all()
     torch.cuda.synchronize()
     _close(dx, dy.float() @ w.float(), 2e-3, "pair_dx")
@@ -116,6 +134,8 @@ def test_wgrad_split256(cuda, Nn, K, M):
             dw = torch.full((Nn, K), 0.5, device="cuda")
             db = torch.full((Nn,), 0.25, device="cuda")
             G.wgrad(dy, x, dw, beta=1.0, red=red, db=db)
+            ll = G.last_launch()
+            assert (ll.family == "gemm8p_kernel" and ll.split_k > 1) if on else ll.family == "gemm_kernel", ll
             red.flush_all()
             torch.cuda.synchronize()
         finally:
@@ -140,6 +160,8 @@ def test_lmhead_dgrad_cb3(cuda):
         old = L.dtc_gemm_set_big_cb3(on)
         try:
             out = G.linear(dy, wt, out_dtype=torch.float32)
+            ll = G.last_launch()
+            assert (ll.family, ll.bm, ll.bn, ll.sub, ll.split_k) == ("gemm8p_kernel", 256, 192 if on else 256, 3 if on else 4, 2), ll
             torch.cuda.synchronize()
         finally:
             L.dtc_gemm_set_big_cb3(old)
@@ -170,12 +192,19 @@ def test_r8_epilogues(cuda, M, Nn, K):
     for mask in (7, 0):
         old = L.dtc_gemm_set_r8(mask)
         try:
+            fams = []
             y = G.linear(x, w, b)
+            fams.append(G.last_launch().family)
             gg, g = G.linear_gelu(x, w, b)
+            fams.append(G.last_launch().family)
             yf = G.linear(x, w, b, out_dtype=torch.float32)
+            fams.append(G.last_launch().family)
             dg = G.matmul_nt_dgelu(dy, w, u)
+            fams.append(G.last_launch().family)
             dn = G.matmul_nn_dgelu(dy, wkn, u)
+            fams.append(G.last_launch().family)
             torch.cuda.synchronize()
+            assert all((f == "gemm8r_kernel") == (mask == 7) for f in fams), (mask, fams)
         finally:
             L.dtc_gemm_set_r8(old)
         _close(y, ref, 1e-2, f"store_bf16 r8={mask}")

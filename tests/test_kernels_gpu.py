@@ -78,14 +78,19 @@ def test_gemm_resid_gelu(cuda):
 @pytest.mark.parametrize("N,K", [(512, 512), (512, 2048), (2048, 512), (1536, 512)])
 def test_gemm_reference_shape_epilogues(cuda, N, K):
     """Every forward / dgrad epilogue at the reference model's Dense shapes (4096 tokens): these are
-    the shapes the 8-wave DMA kernels (csrc/gemm.hip gemm_dmaw_kernel) are planned for."""
+    the shapes the 8-wave DMA kernels (csrc/gemm.hip gemm_dmaw_kernel) are planned for -- in the default
+    plan the fp32 residual forwards of the d_model-wide outputs (N = 512: 128 x 64 tiles); the wider ones
+    keep the register-staged 128^2 kernel."""
     M = 4096
     x, w = _r(M, K, seed=41), _r(N, K, scale=0.05, seed=42)
     b = _r(N, dtype=torch.float32, seed=43)
     res = _r(M, N, dtype=torch.float32, seed=44)
     ref = x.float() @ w.float().t() + b
     _close(G.linear(x, w, b), ref, 1e-2, "store_bf16")
-    _close(G.linear_resid(x, w, b, res), res + ref, 2e-3, "resid")
+    yr = G.linear_resid(x, w, b, res)
+    ll = G.last_launch()
+    assert (ll.family, ll.bm, ll.bn) == (("gemm_dmaw_kernel", 128, 64) if N == 512 else ("gemm_kernel", 128, 128)), ll
+    _close(yr, res + ref, 2e-3, "resid")
     u, g = G.linear_gelu(x, w, b)
     _close(u, G.gelu_tanh_grad(ref), 1e-2, "gelu_grad")
     _close(g, G.gelu_tanh(ref), 1e-2, "gelu")
@@ -342,6 +347,8 @@ def test_lmhead_ce(cuda, M, D, V, Vp):
     b = _r(Vp, dtype=torch.float32, seed=24)
     labels = torch.randint(0, V, (M,), dtype=torch.int32)
     logits, rowstat, lab = X.lmhead_logits_partials(h, w, b, labels.to(cuda), 0, V)
+    ll = G.last_launch()
+    assert (ll.family, ll.bm, ll.bn) == (("gemm8p_kernel", 256, 256) if Vp == 50304 else ("gemm_kernel", 128, 128)), ll
     lse, loss = X.ce_finalize(rowstat.unsqueeze(0).contiguous(), lab, 1.0 / M)
     ref = torch.nn.functional.cross_entropy(h.float().cpu() @ w.float().cpu()[:V].t() + b.cpu()[:V], labels.long())
     assert abs(loss.item() - ref.item()) < 2e-2 * abs(ref.item()), (loss.item(), ref.item())
@@ -561,6 +568,7 @@ def test_gemm_resid_ln_fused(cuda, M, D, K):
     sync = LF.LnSync(cuda, M, D, nsites=2, step=step)
     for it in range(2):
         x, (y, mu, rs) = LF.linear_resid_ln(a, w, b, res, g, be, 1e-6, sync, site=it)
+        assert G.last_launch()[:5] == ("gemm_dmaw_kernel_ln", 128, 64, 1, 0), G.last_launch()
         xr = res + a.float() @ w.float().t() + b
         _close(x, xr, 2e-5, "x")
         mr = xr.mean(-1)
@@ -589,6 +597,7 @@ def test_dgrad_ln_bwd_fused(cuda, M, D, K, nslab):
     outs = [torch.zeros(D, device=cuda) for _ in range(3)]
     dbias = outs[2] if nslab == 3 else None
     dx, dxc = LF.dgrad_ln_bwd(dY, wt, x, g, mu, rs, dres, outs[0], outs[1], 0.0, dbias=dbias, sync=sync, site=2)
+    assert G.last_launch()[:5] == ("gemm_dmaw_kernel_ln", 128, 64, 1, 1), G.last_launch()
     refs = [torch.zeros(D, device=cuda) for _ in range(3)]
     dy = G.linear_resid(dY, wt, None, None)
     dxr = LN.layernorm_bwd(dy, x, g, mu, rs, dres, refs[0], refs[1], 0.0, dbias=refs[2] if nslab == 3 else None)
