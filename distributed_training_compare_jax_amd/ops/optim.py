@@ -95,14 +95,17 @@ def adamw_flat(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
     if not p.is_cuda:
         if enable is not None and float(enable.item()) == 0.0:
             return
-        t = float(step.item())
-        norm = float(sumsq.item()) ** 0.5
-        scale = 1.0 if (max_norm <= 0 or norm < max_norm) else max_norm / norm
+        # the hyperparameters as the kernel gets them: fp32 roundings, 1 - b formed in fp32 (1 - 0.999 in double
+        # rounds to an fp32 1.3e-5 away from 1.f - 0.999f)
+        lr, b1, b2, eps, wd, mx = (torch.tensor(x, dtype=torch.float32) for x in (lr, b1, b2, eps, wd, max_norm))
+        t = step[0].float()
+        norm = sumsq[0].float().sqrt()
+        scale = mx / norm if (max_norm > 0 and not bool(norm < mx)) else torch.tensor(1.0)
         gg = g * scale
-        m.mul_(b1).add_(gg, alpha=1 - b1)
-        v.mul_(b2).addcmul_(gg, gg, value=1 - b2)
-        mhat = m / (1 - b1 ** t)
-        vhat = v / (1 - b2 ** t)
+        m.mul_(b1).add_((1 - b1) * gg)
+        v.mul_(b2).add_(((1 - b2) * gg) * gg)
+        mhat = m / (1 - torch.pow(b1, t))
+        vhat = v / (1 - torch.pow(b2, t))
         p.sub_(lr * (mhat / (vhat.sqrt() + eps) + wd * p))
         if mirror is not None and n_mirror > 0:
             mirror[:n_mirror].copy_(p[:n_mirror])
