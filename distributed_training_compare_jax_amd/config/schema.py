@@ -180,6 +180,9 @@ MODEL_PRESETS: Dict[str, Dict[str, Any]] = {
                        name="gpt2-small-124M"),
     "gpt2-medium": dict(d_model=1024, n_layers=24, n_heads=16, d_ff=4096, max_seq_len=1024, dropout=0.1,
                         name="gpt2-medium-355M"),
+    # GPT-3 XL's shape with 16 heads of 128 (the wide LayerNorm kernels + head_dim 128 attention)
+    "gpt-1.3b": dict(d_model=2048, n_layers=24, n_heads=16, d_ff=8192, max_seq_len=2048, dropout=0.1,
+                     name="gpt-1.3b"),
     "tiny": dict(d_model=64, n_layers=2, n_heads=2, d_ff=256, max_seq_len=64, dropout=0.1, name="tiny"),
 }
 

@@ -4,7 +4,8 @@
 // float4 chunks (16-byte loads), two-pass mean/variance in fp32, output in the GEMM operand
 // dtype.  Backward fuses the residual-gradient add and writes a bf16 copy of dx for the next
 // dgrad/wgrad GEMM; dgamma/dbeta go through per-block partial slabs + an ordered reduce (no
-// float atomics -> bitwise reproducible).
+// float atomics -> bitwise reproducible).  Rows wider than a wave can hold (forward D > 2048, backward
+// D > 1024, up to 8192) are spread over the waves of a block: the ln_*_wide kernels below.
 #include "common.h"
 #include <cstdlib>
 
@@ -213,6 +214,227 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const void* __restrict__ dy
   }
 }
 
+// ---- wide rows: forward 2048 < D <= 8192, backward 1024 < D <= 8192 ----
+// A row no longer fits one wave's registers next to gamma / the column accumulators, so the W waves of a
+// block (4 up to D 4096, 8 above: at most 4 f32x4 per lane either way) each own a contiguous 1/W of the
+// columns (NV f32x4 per lane, chunk wave*NV*64 + lane + 64*i, NV = ceil(D / (256 W))) and walk the SAME rows.
+// Row sums: each wave reduces its share (warp_sum), the W wave sums meet in a few floats of LDS and every
+// wave adds them in one fixed pairwise order: one barrier per exchange, the LDS buffer alternating between
+// row groups so no second barrier is needed.  The column partials of the backward are exclusive to the
+// owning wave and go straight to the slab: no block reduction, no LDS beyond the exchange (<= 512 B).
+constexpr int LNW_MAX_D = 8192;
+// rows per group: a lane has 6-8 (fwd) / 18-24 (bwd) 16-byte loads in flight per group, as the narrow kernels
+// have at their widest
+__host__ __device__ constexpr int lnw_rows(int NV) { return NV <= 2 ? 4 : 2; }
+
+// sum over the block's W waves of a per-wave value, R values at once; buf is [R][W] floats of LDS
+template <int R, int W>
+__device__ __forceinline__ void lnw_block_sum(float (&v)[R], float* buf, int lane, int wave) {
+  static_assert(W == 4 || W == 8, "pairwise order below");
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < R; ++q) buf[q * W + wave] = v[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < R; ++q) {
+    const float* p = buf + q * W;
+    float t = (p[0] + p[1]) + (p[2] + p[3]);
+    if constexpr (W == 8) t += (p[4] + p[5]) + (p[6] + p[7]);
+    v[q] = t;
+  }
+}
+
+// one group of R rows per block; same two-pass statistics, residual add and outputs as ln_fwd_kernel
+template <int NV, int W, bool XB>
+__global__ void __launch_bounds__(64 * W) ln_fwd_wide_kernel(const void* x, const float* __restrict__ resid, float* x_out,
+                                                          const float* __restrict__ g, const float* __restrict__ b,
+                                                          void* __restrict__ y, float* __restrict__ mean_out,
+                                                          float* __restrict__ rstd_out, int M, int D, float eps,
+                                                          int out_f32) {
+  constexpr int R = lnw_rows(NV);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row0 = blockIdx.x * R;
+  const int D4 = D / 4, cbase = wave * NV * 64 + lane;
+  DTC_ASSERT(D % 4 == 0 && D4 <= NV * 64 * W && row0 < M && wave < W && cbase + 64 * (NV - 1) < NV * 64 * W);
+  __shared__ float xs[2][R * W];
+  f32x4 v[R][NV], gv[NV], bv[NV];
+#pragma unroll
+  for (int q = 0; q < R; ++q) {
+    const long off = (long)min(row0 + q, M - 1) * D;  // a row past M re-reads row M-1 and stores nothing
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = cbase + 64 * i;
+      if (c < D4) {
+        if constexpr (XB) {
+          const bf16x4 t = ((const bf16x4*)((const bf16*)x + off))[c];
+          v[q][i] = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+        } else {
+          v[q][i] = ((const f32x4*)((const float*)x + off))[c];
+        }
+      } else {
+        v[q][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    if (resid) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = cbase + 64 * i;
+        if (c < D4) v[q][i] += ((const f32x4*)(resid + off))[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = cbase + 64 * i;
+    gv[i] = c < D4 ? ((const f32x4*)g)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+    bv[i] = c < D4 ? ((const f32x4*)b)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float s[R], qs[R];
+#pragma unroll
+  for (int q = 0; q < R; ++q) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) t += v[q][i][0] + v[q][i][1] + v[q][i][2] + v[q][i][3];
+    s[q] = warp_sum(t);
+  }
+  lnw_block_sum<R, W>(s, xs[0], lane, wave);
+#pragma unroll
+  for (int q = 0; q < R; ++q) {
+    s[q] = s[q] / D;  // the mean
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      if (cbase + 64 * i < D4) {
+        f32x4 d = v[q][i] - s[q];
+        t += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+      }
+    }
+    qs[q] = warp_sum(t);
+  }
+  lnw_block_sum<R, W>(qs, xs[1], lane, wave);
+#pragma unroll
+  for (int q = 0; q < R; ++q) {
+    const int row = row0 + q;
+    const float mean = s[q], rstd = rsqrtf(qs[q] / D + eps);
+    if (row >= M) continue;
+    if (threadIdx.x == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+    if (x_out) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = cbase + 64 * i;
+        if (c < D4) ((f32x4*)(x_out + (long)row * D))[c] = v[q][i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = cbase + 64 * i;
+      if (c < D4) {
+        f32x4 o = (v[q][i] - mean) * rstd * gv[i] + bv[i];
+        if (out_f32) ((f32x4*)((float*)y + (long)row * D))[c] = o;
+        else ((bf16x4*)((bf16*)y + (long)row * D))[c] = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
+      }
+    }
+  }
+}
+
+// `groups` row groups of R rows per block (R * groups = the narrow kernel's rows per block, so the partial
+// slab has the same [blocks][nslab][D] shape); same slabs and outputs as ln_bwd_kernel
+template <int NV, int W>
+__global__ void __launch_bounds__(64 * W) ln_bwd_wide_kernel(const void* __restrict__ dy, int dy_f32, const float* __restrict__ x,
+                                                          const float* __restrict__ g, const float* __restrict__ mean,
+                                                          const float* __restrict__ rstd, const float* __restrict__ dres,
+                                                          float* __restrict__ dx, bf16* __restrict__ dx_c,
+                                                          float* __restrict__ part, int nslab, int M, int D, int groups) {
+  constexpr int R = lnw_rows(NV);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int D4 = D / 4, cbase = wave * NV * 64 + lane;
+  DTC_ASSERT(D % 4 == 0 && D4 <= NV * 64 * W && wave < W && cbase + 64 * (NV - 1) < NV * 64 * W && nslab >= 2 && nslab <= 3 &&
+             (long)blockIdx.x * R * groups < M);
+  __shared__ float xs[2][2 * R * W];
+  f32x4 ag[NV], ab[NV], ao[NV], gv[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    ag[i] = f32x4{0.f, 0.f, 0.f, 0.f}; ab[i] = ag[i]; ao[i] = ag[i];
+    const int c = cbase + 64 * i;
+    gv[i] = c < D4 ? ((const f32x4*)g)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int it = 0; it < groups; ++it) {
+    const int r0 = (blockIdx.x * groups + it) * R;  // block-uniform: every wave reaches the barrier below
+    f32x4 xh[R][NV], d[R][NV], rv[R][NV];
+    float ss[2 * R], rsv[R];
+    // every global load of the row group is issued before the first reduction
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      const int row = r0 + q;
+      const bool ok = row < M;
+      const float mu = ok ? mean[row] : 0.f;
+      rsv[q] = ok ? rstd[row] : 0.f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = cbase + 64 * i;
+        f32x4 xv = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f}, rr = {0.f, 0.f, 0.f, 0.f};
+        if (ok && c < D4) {
+          xv = ((const f32x4*)(x + (long)row * D))[c];
+          if (dy_f32) dv = ((const f32x4*)((const float*)dy + (long)row * D))[c];
+          else { bf16x4 t = ((const bf16x4*)((const bf16*)dy + (long)row * D))[c]; dv = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]}; }
+          if (dres) rr = ((const f32x4*)(dres + (long)row * D))[c];
+        }
+        xh[q][i] = (xv - mu) * rsv[q];
+        d[q][i] = dv;
+        rv[q][i] = rr;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        if (cbase + 64 * i < D4) {
+          f32x4 gd = d[q][i] * gv[i];
+          s1 += gd[0] + gd[1] + gd[2] + gd[3];
+          f32x4 t2 = gd * xh[q][i];
+          s2 += t2[0] + t2[1] + t2[2] + t2[3];
+          ag[i] += d[q][i] * xh[q][i];
+          ab[i] += d[q][i];
+        }
+      }
+      ss[2 * q] = warp_sum(s1);
+      ss[2 * q + 1] = warp_sum(s2);
+    }
+    lnw_block_sum<2 * R, W>(ss, xs[it & 1], lane, wave);
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      const int row = r0 + q;
+      const float c1 = ss[2 * q] / D, c2 = ss[2 * q + 1] / D;
+      if (row >= M) continue;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = cbase + 64 * i;
+        if (c < D4) {
+          f32x4 gd = d[q][i] * gv[i];
+          f32x4 o = (gd - c1 - xh[q][i] * c2) * rsv[q];
+          if (dres) o += rv[q][i];
+          ((f32x4*)(dx + (long)row * D))[c] = o;
+          if (dx_c) ((bf16x4*)(dx_c + (long)row * D))[c] = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
+          ao[i] += o;
+        }
+      }
+    }
+  }  // row groups
+  // this wave's columns of the block's partial row: part[block][nslab][D]
+  float* pb = part + (long)blockIdx.x * nslab * D;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = cbase + 64 * i;
+    if (c < D4) {
+      ((f32x4*)pb)[c] = ag[i];
+      ((f32x4*)(pb + D))[c] = ab[i];
+      if (nslab > 2) ((f32x4*)(pb + 2 * (long)D))[c] = ao[i];
+    }
+  }
+}
+
 // out (beta*out +)= sum_p part[p*C + c], c in [0, C), the C columns cut into segments of `seg`
 // columns routed to o0 / o1 / o2.  Block = 32 columns x 8 partial groups (whole 128-B row segments; 16
 // columns read half lines), LDS tree over the groups — deterministic order, P/8 loads per thread, 8 in
@@ -373,11 +595,46 @@ __global__ void __launch_bounds__(256) reduce_tasks_kernel(RedBatch batch) {
     default: return 2001;                                                    \
   }
 
+// the wide kernels: W waves per block and NV = ceil(D / (256 W)) f32x4 per lane, 2..4
+#define DTC_NVW_SWITCH(D_, ...)                                                                   \
+  if ((D_) <= 4096) {                                                                             \
+    constexpr int WC = 4;                                                                         \
+    switch (((D_) + 1023) / 1024) {                                                               \
+      case 2: { constexpr int NVC = 2; __VA_ARGS__; } break;                                      \
+      case 3: { constexpr int NVC = 3; __VA_ARGS__; } break;                                      \
+      case 4: { constexpr int NVC = 4; __VA_ARGS__; } break;                                      \
+      default: return 2001;                                                                       \
+    }                                                                                             \
+  } else {                                                                                        \
+    constexpr int WC = 8;                                                                         \
+    switch (((D_) + 2047) / 2048) {                                                               \
+      case 3: { constexpr int NVC = 3; __VA_ARGS__; } break;                                      \
+      case 4: { constexpr int NVC = 4; __VA_ARGS__; } break;                                      \
+      default: return 2001;                                                                       \
+    }                                                                                             \
+  }
+
+// LayerNorm widths: D % 4 == 0 (16-byte chunks) and D <= 8192.  The forward keeps a row per wave up to 2048
+// and the backward up to 1024 (its block reduction holds 3 x 4 x D floats of LDS); wider rows take the
+// kernels that spread a row over the block's waves.
+constexpr int LN_FWD_NARROW_D = 2048, LN_BWD_NARROW_D = 1024;
+static inline int ln_width_error(int D) { return D <= 0 || D % 4 ? 2002 : (D > LNW_MAX_D ? 2001 : 0); }
+
+template <bool XB>
+static int ln_fwd_wide_launch(const void* x, const float* resid, float* x_out, const float* g, const float* b, void* y,
+                              float* mean, float* rstd, int M, int D, float eps, int out_f32, hipStream_t st) {
+  DTC_NVW_SWITCH(D, hipLaunchKernelGGL((ln_fwd_wide_kernel<NVC, WC, XB>), dim3((M + lnw_rows(NVC) - 1) / lnw_rows(NVC)),
+                                       dim3(64 * WC), 0, st, x, resid, x_out, g, b, y, mean, rstd, M, D, eps, out_f32));
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" {
 
 int dtc_add_layernorm_fwd(const float* x, const float* resid, float* x_out, const float* g, const float* b, void* y,
                           float* mean, float* rstd, int M, int D, float eps, int out_f32, hipStream_t st) {
-  if (D % 4) return 2002;
+  if (const int e = ln_width_error(D)) return e;
+  if (D > LN_FWD_NARROW_D) return ln_fwd_wide_launch<false>(x, resid, x_out, g, b, y, mean, rstd, M, D, eps, out_f32, st);
   int nv = (D / 4 + 63) / 64;
   // one row per wave (two rows per wave measured neutral on GPT-2 small, round 3: removed)
   dim3 grid((M + 3) / 4);
@@ -390,8 +647,9 @@ int dtc_add_layernorm_fwd(const float* x, const float* resid, float* x_out, cons
 // x_out = (fp32) d + resid with d bf16 (a bf16 out_proj / fc2 output, DTC_FWD_BF16), then LayerNorm(x_out)
 int dtc_add_layernorm_fwd_bf16(const bf16* d, const float* resid, float* x_out, const float* g, const float* b,
                                void* y, float* mean, float* rstd, int M, int D, float eps, int out_f32, hipStream_t st) {
-  if (D % 4) return 2002;
+  if (const int e = ln_width_error(D)) return e;
   DTC_HOST_CHECK(d && resid && x_out && (const void*)d != (const void*)x_out);
+  if (D > LN_FWD_NARROW_D) return ln_fwd_wide_launch<true>(d, resid, x_out, g, b, y, mean, rstd, M, D, eps, out_f32, st);
   int nv = (D / 4 + 63) / 64;
   dim3 grid((M + 3) / 4);
   DTC_NV_SWITCH(nv, hipLaunchKernelGGL((ln_fwd_kernel<NVC, 1, true>), grid, dim3(256), 0, st, d, resid, x_out, g, b, y,
@@ -422,14 +680,23 @@ long dtc_layernorm_bwd_workspace_bytes(int M, int D) {
 int dtc_layernorm_bwd(const void* dy, int dy_f32, const float* x, const float* g, const float* mean, const float* rstd,
                       const float* dres, float* dx, bf16* dx_c, float* dg, float* db, float* dbias, int M, int D,
                       int accumulate, float* ws, long ws_bytes, int defer, hipStream_t st) {
-  if (D % 4 || D > 1024) return 2002;  // dgamma/dbeta block reduce holds D <= 1024 in LDS
+  if (const int e = ln_width_error(D)) return e;  // D % 4 == 0 and D <= 8192 (see ln_width_error)
   const int iters = ln_bwd_iters();
   int blocks = (M + LN_BWD_ROWS * iters - 1) / (LN_BWD_ROWS * iters);
   if (ws_bytes < dtc_layernorm_bwd_workspace_bytes(M, D)) return 2003;
-  int nv = (D / 4 + 63) / 64;
   const int nslab = dbias ? 3 : 2;
-  DTC_NV_SWITCH(nv, hipLaunchKernelGGL(ln_bwd_kernel<NVC>, dim3(blocks), dim3(256), 0, st, dy, dy_f32, x, g, mean, rstd,
-                                       dres, dx, dx_c, ws, nslab, M, D, iters));
+  if (D > LN_BWD_NARROW_D) {
+    // same rows per block as the narrow kernel (LN_BWD_ROWS * iters, a multiple of every lnw_rows), so the
+    // partials are [blocks][nslab][D] with the same `blocks` and dtc_layernorm_bwd_workspace_bytes holds
+    static_assert(LN_BWD_ROWS % 4 == 0, "lnw_rows must divide the rows per block");
+    DTC_HOST_CHECK(((uintptr_t)ws & 15) == 0);  // the partial rows are stored as f32x4
+    DTC_NVW_SWITCH(D, hipLaunchKernelGGL((ln_bwd_wide_kernel<NVC, WC>), dim3(blocks), dim3(64 * WC), 0, st, dy, dy_f32, x, g,
+                                         mean, rstd, dres, dx, dx_c, ws, nslab, M, D, LN_BWD_ROWS * iters / lnw_rows(NVC)));
+  } else {
+    int nv = (D / 4 + 63) / 64;
+    DTC_NV_SWITCH(nv, hipLaunchKernelGGL(ln_bwd_kernel<NVC>, dim3(blocks), dim3(256), 0, st, dy, dy_f32, x, g, mean, rstd,
+                                         dres, dx, dx_c, ws, nslab, M, D, iters));
+  }
   DTC_CHECK_LAUNCH();
   if (defer) return 0;  // partials stay in ws: [blocks][nslab][D] (a RED_TALL task per slab)
   hipLaunchKernelGGL(slab_reduce, dim3((nslab * D + SR_COLS - 1) / SR_COLS), dim3(256), 0, st, ws, blocks, nslab * D, dg, db, dbias,

@@ -121,8 +121,10 @@ class GPTStage:
         # launch per layer (ops/reduce.py).  (A second stream for the weight gradients measured slower on
         # one GPU -- 6.00 vs 5.44 ms, round 2 -- and was removed: the grouped launches fill the chip instead.)
         dev = torch.device(flat.device)
-        # 512 MB window: a layer's split-K weight-gradient slabs (GPT-2 medium: 4 x ~67 MB) + LN partials
-        self.red = GradReducer(dev, arena_mb=512) if dev.type == "cuda" else None
+        # 512 MB window: a layer's split-K weight-gradient slabs (GPT-2 medium: 4 x ~67 MB) + LN partials;
+        # past GPT-2 medium the window grows with a layer's fp32 weights (medium: 48 MB -> 512, gpt-1.3b: 192 MB -> 2048)
+        layer_bytes = 4 * (4 * cfg.d_model * cfg.d_model + 2 * cfg.d_model * cfg.d_ff)
+        self.red = GradReducer(dev, arena_mb=max(512, (32 * layer_bytes // 3) >> 20)) if dev.type == "cuda" else None
         self._bias_fused = set()  # layers whose fc2.b grad an upstream LN backward already produced
         # deferred optimizer (train/engine.py): params of layer l / "head" become valid when this
         # event fires; the forward waits on it right before first use

@@ -4,7 +4,8 @@ Reference sites: ``model/TransformerBlock.py:16,22`` and the final LN ``model/GP
 Input is the fp32 residual stream; output is the GEMM operand dtype (bf16 on GPU).  The
 backward fuses the residual-gradient add (``dx = dres + LN'(dy)``) and emits per-row-block
 partials for ``dγ, dβ`` that are reduced deterministically (no float atomics).
-GPU path: ``csrc/layernorm.hip`` (one wave64 per row, vectorised 16-B loads).
+GPU path: ``csrc/norm_reduce.hip`` (vectorised 16-B loads; one wave64 per row up to d_model 2048 forward /
+1024 backward, a row spread over the 4 or 8 waves of a block up to 8192; ``D % 4 == 0``).
 """
 
 from __future__ import annotations
