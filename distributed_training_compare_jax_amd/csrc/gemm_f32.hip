@@ -330,29 +330,40 @@ PlanF plan_f32(int M, int N, int K) {
   return PlanF{ct, ct, split, kps, tm, tn};
 }
 
+// Record of the last launch, written by the launch site from the kernel's own template arguments and the
+// GemmF it passes (never recomputed from plan_f32, so it cannot drift from what was launched); read by
+// dtc_gemm_f32_last_launch (tests assert the variant a shape lands on, as with gemm.hip's note_launch).
+struct LastLaunchF {
+  int bm, bn, bk, split, kps, layout, epi, split_off;
+};
+static LastLaunchF g_last_f32{};
+
+// split_off: the plan asked for split-K and the "not splittable" rule of dtc_gemm_f32 switched it off
 template <int TM, int TN, bool AK, bool BKM, int EPI>
-int launch_f32(const GemmF& g, hipStream_t st) {
+int launch_f32(const GemmF& g, bool split_off, hipStream_t st) {
   const int blocks = g.tiles_m * g.tiles_n * g.split;
   hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, AK, BKM, EPI>), dim3(blocks), dim3(NTF), 0, st, g);
   DTC_CHECK_LAUNCH();
+  g_last_f32 = LastLaunchF{64 * TM, 64 * TN, bk_of<TM, TN>(), g.split, g.kps, AK ? (BKM ? 0 : 1) : 2, EPI,
+                           split_off ? 1 : 0};
   return 0;
 }
 
 template <bool AK, bool BKM, int EPI>
-int launch_tiles(const GemmF& g, const PlanF& p, hipStream_t st) {
-  if (p.tm == 2 && p.tn == 2) return launch_f32<2, 2, AK, BKM, EPI>(g, st);
-  if (p.tm == 2 && p.tn == 1) return launch_f32<2, 1, AK, BKM, EPI>(g, st);
-  return launch_f32<1, 1, AK, BKM, EPI>(g, st);
+int launch_tiles(const GemmF& g, const PlanF& p, bool split_off, hipStream_t st) {
+  if (p.tm == 2 && p.tn == 2) return launch_f32<2, 2, AK, BKM, EPI>(g, split_off, st);
+  if (p.tm == 2 && p.tn == 1) return launch_f32<2, 1, AK, BKM, EPI>(g, split_off, st);
+  return launch_f32<1, 1, AK, BKM, EPI>(g, split_off, st);
 }
 
 template <bool AK, bool BKM>
-int launch_epi(const GemmF& g, const PlanF& p, int epi, hipStream_t st) {
+int launch_epi(const GemmF& g, const PlanF& p, int epi, bool split_off, hipStream_t st) {
   switch (epi) {
-    case EPI_STORE: return launch_tiles<AK, BKM, EPI_STORE>(g, p, st);
-    case EPI_RESID: return launch_tiles<AK, BKM, EPI_RESID>(g, p, st);
-    case EPI_GELU: return launch_tiles<AK, BKM, EPI_GELU>(g, p, st);
-    case EPI_DGELU: return launch_tiles<AK, BKM, EPI_DGELU>(g, p, st);
-    case EPI_LMHEAD: return launch_tiles<AK, BKM, EPI_LMHEAD>(g, p, st);
+    case EPI_STORE: return launch_tiles<AK, BKM, EPI_STORE>(g, p, split_off, st);
+    case EPI_RESID: return launch_tiles<AK, BKM, EPI_RESID>(g, p, split_off, st);
+    case EPI_GELU: return launch_tiles<AK, BKM, EPI_GELU>(g, p, split_off, st);
+    case EPI_DGELU: return launch_tiles<AK, BKM, EPI_DGELU>(g, p, split_off, st);
+    case EPI_LMHEAD: return launch_tiles<AK, BKM, EPI_LMHEAD>(g, p, split_off, st);
     default: return (int)hipErrorInvalidValue;
   }
 }
@@ -372,6 +383,15 @@ long dtc_gemm_f32_workspace_bytes(int layout, int M, int N, int K) {
 int dtc_lmhead_nparts_f32(int M, int N, int K) {
   const PlanF p = plan_f32(M, N, K);
   return p.tiles_n * 2;
+}
+
+// the record of the last dtc_gemm_f32 launch (LastLaunchF): out[8] = BM, BN, BK, split, kps, layout, epilogue,
+// split switched off
+int dtc_gemm_f32_last_launch(int* out) {
+  const LastLaunchF l = g_last_f32;
+  out[0] = l.bm; out[1] = l.bn; out[2] = l.bk; out[3] = l.split;
+  out[4] = l.kps; out[5] = l.layout; out[6] = l.epi; out[7] = l.split_off;
+  return 0;
 }
 
 int dtc_gemm_f32(const GemmArgs* a, hipStream_t st) {
@@ -398,7 +418,8 @@ int dtc_gemm_f32(const GemmArgs* a, hipStream_t st) {
   // split's k range
   auto fits = [](long elems) { return elems * 4 < 0x7fffffffL; };
   const bool splittable = a->epi == EPI_STORE && a->bias == nullptr && a->alpha == 1.f;
-  if (p.split > 1 && !splittable) {  // epilogues that need the full sum in registers: no split-K
+  const bool split_off = p.split > 1 && !splittable;
+  if (split_off) {  // epilogues that need the full sum in registers: no split-K
     p.split = 1;
     p.kps = a->K;
   }
@@ -409,9 +430,9 @@ int dtc_gemm_f32(const GemmArgs* a, hipStream_t st) {
   g.slab = (float*)a->workspace;
   if (a->epi == EPI_LMHEAD && a->layout != 0) return (int)hipErrorInvalidValue;
   int rc;
-  if (a->layout == 0) rc = launch_epi<true, true>(g, p, a->epi, st);
-  else if (a->layout == 1) rc = launch_epi<true, false>(g, p, a->epi, st);
-  else rc = launch_epi<false, false>(g, p, a->epi, st);
+  if (a->layout == 0) rc = launch_epi<true, true>(g, p, a->epi, split_off, st);
+  else if (a->layout == 1) rc = launch_epi<true, false>(g, p, a->epi, split_off, st);
+  else rc = launch_epi<false, false>(g, p, a->epi, split_off, st);
   if (rc) return rc;
   if (p.split > 1) {
     const long MN = (long)a->M * a->N;

@@ -186,6 +186,7 @@ def _declare(lib):
         # exact-fp32 parity path (csrc/gemm_f32.hip, csrc/attention_f32.hip)
         "dtc_gemm_f32": ([ctypes.POINTER(GemmArgs), vp], i),
         "dtc_gemm_f32_workspace_bytes": ([i, i, i, i], l),
+        "dtc_gemm_f32_last_launch": ([ctypes.POINTER(c_int)], i),
         "dtc_lmhead_nparts_f32": ([i, i, i], i),
         "dtc_attn_f32_fwd": ([vp, vp, vp, i, i, i, i, f, vp], i),
         "dtc_attn_f32_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, f, vp, l, vp], i),

@@ -143,6 +143,20 @@ def last_launch() -> LastLaunch:
     return LastLaunch(FAMILIES[v[0]], *v[1:])
 
 
+LastLaunchF32 = collections.namedtuple("LastLaunchF32", "bm bn bk split kps layout epi split_off")
+
+
+def last_launch_f32() -> LastLaunchF32:
+    """What the last exact-fp32 GEMM launch of this process ran (csrc/gemm_f32.hip ``launch_f32``, written from the
+    kernel's own template arguments): the tile ``bm`` x ``bn`` (64*TM x 64*TN), its k-tile ``bk``, the split-K
+    factor ``split`` with ``kps`` k per slab, ``layout`` (0 nt, 1 nn, 2 tn), the epilogue id ``epi`` and
+    ``split_off`` = 1 when the plan asked for split-K and the epilogue (bias, alpha or a fused one) switched it
+    off.  Tests assert it; nothing on the hot path reads it."""
+    out = (ctypes.c_int * 8)()
+    N.check(N.lib().dtc_gemm_f32_last_launch(out), "dtc_gemm_f32_last_launch")
+    return LastLaunchF32(*out)
+
+
 def _check2d(t: torch.Tensor, name: str):
     if t.dim() != 2 or t.stride(1) != 1:
         raise ValueError(f"{name}: expected a row-major 2-D tensor, got shape {tuple(t.shape)} strides {t.stride()}")
