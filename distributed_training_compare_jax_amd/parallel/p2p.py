@@ -9,7 +9,9 @@ slice (all-gather), through IPC-mapped peer buffers.
 Being ordinary stream-ordered kernels (barriers are device-side epoch flags), the collective is
 captured INTO the step's hipGraph: the TP step no longer cuts its graph at every all-reduce the
 way an eager RCCL call does.  The sum runs in rank order on every rank, so TP replicas stay
-bitwise identical.  RCCL remains the path for anything else (scalars, non-fp32, oversize).
+bitwise identical (``tests/test_p2p_collectives_gpu.py`` pins every output bit at 2, 3, 5 and 8
+ranks).  RCCL remains the path for anything else (non-fp32 all-reduces, oversize); scalars and
+slots of fewer than 4 floats go through zero-padded vector elements (``parallel.tp.TPComm``).
 
 Handles are exchanged once over the process group (``all_gather_object``), so the same code runs
 on a real node (RCCL group) and in the one-GPU multi-process tests (gloo group, all ranks on one
@@ -115,7 +117,7 @@ class P2PAllReduce:
 
     def all_reduce_(self, t: torch.Tensor, mode: int = 0) -> torch.Tensor:
         """In-place sum over the group.  mode 0: one-shot (one barrier, every rank reads every peer) at
-        W = 2 and for small messages (<= 1 MB at W <= 4, 512 KB at W = 8), else two-shot (reduce-scatter
+        W = 2 and for small messages (<= 1 MiB at W <= 4, <= 512 KiB at W >= 5), else two-shot (reduce-scatter
         + all-gather, 2 (W-1)/W of the bytes per rank); 1 / 2 force two-shot / one-shot."""
         N.check(N.lib().dtc_p2p_allreduce(t.data_ptr(), t.data_ptr(), t.numel(), self._bases_ptr, self.rank, self.world,
                                           self.half, self.epoch.data_ptr(), self.err.data_ptr(), int(mode),
@@ -171,6 +173,8 @@ class P2PAllReduce:
     def reduce_scatter(self, x, rows: int, cols: int, dtype, out: torch.Tensor, resid=None, bias=None) -> torch.Tensor:
         """out (fp32 [rows / W, cols], this rank's rows) = resid + bias + Σ_ranks x[own rows]; ``x`` the full
         [rows, cols] partial (bf16 / fp32) or None when its producer wrote it into :meth:`staged_out`."""
+        if rows % self.world:  # rows // W would drop the last rows and shift every rank's slice
+            raise RuntimeError(f"P2P reduce-scatter: {rows} rows do not divide over {self.world} ranks")
         n_loc = rows // self.world * cols
         N.check(N.lib().dtc_p2p_reduce_scatter(N.ptr(x), int(dtype == torch.bfloat16), out.data_ptr(), n_loc,
                                                self._bases_ptr, self.rank, self.world, self.half,
@@ -198,17 +202,23 @@ class P2PAllReduce:
         Also checks the buffer-half invariant :meth:`staged_out` relies on: every call advances the
         device epoch by 2, replays included, while the host counter only sees calls issued from Python
         (eager or captured), so the device half ``(epoch >> 1) & 1`` must equal the host half ``calls & 1``
-        (true as long as every captured step is padded to an even count by :meth:`end_step`).  A P2P call
-        outside the step (eval, a debug all-reduce) without its own :meth:`end_step` flips it, after which
-        graph replays would reduce the stale half: raise instead."""
+        (true as long as every captured step is padded to an even count by :meth:`end_step`).  What this
+        catches is a captured graph with an ODD call count: the host counts it once, every replay advances
+        the epoch again, and after an even number of replays the two halves differ, so the next
+        :meth:`staged_out` would point at the half the device does not reduce: raise instead.  An
+        :meth:`end_step` alone does not repair that state (it advances both sides); one barrier round the
+        host does not count (``dtc_p2p_barrier_round``), on every rank, does.  NOT caught: an eager call
+        outside the step (eval, a debug all-reduce) without its own :meth:`end_step` advances host and
+        device alike, so this check passes, yet the pointers a captured step got from :meth:`staged_out`
+        are then one half off on replay.  Always pad out-of-step use with :meth:`end_step`."""
         e = int(self.err.item())
         if e:
             raise RuntimeError(f"P2P all-reduce: rank {self.rank} timed out waiting for rank {e - 1000}")
         dev_half = (int(self.epoch.item()) >> 1) & 1
         if dev_half != (self.calls & 1):
             raise RuntimeError(f"P2P all-reduce: rank {self.rank} buffer-half mismatch (device epoch "
-                               f"{int(self.epoch.item())}, host calls {self.calls}): a P2P call outside the step "
-                               "left an odd call count; call end_step() after out-of-step P2P use")
+                               f"{int(self.epoch.item())}, host calls {self.calls}): a captured graph with an odd "
+                               "number of P2P calls was replayed; end every captured step with end_step()")
 
     def close(self):
         L = N.lib()

@@ -82,18 +82,22 @@ class TPComm:
 
     def all_gather_stack(self, t: torch.Tensor) -> torch.Tensor:
         """[...] → [size, ...] (shard-major).  With the P2P path: every rank writes its slot of a
-        zeroed [size, ...] buffer and the buffer is summed (x + 0 = x exactly, so it IS the gather),
-        in-graph, no RCCL call."""
+        zeroed [size, ...] buffer and the buffer is summed, in-graph, no RCCL call.  x + 0 = x in value,
+        so it IS the gather numerically, with one exception in the bits: the sum starts from rank 0's
+        +0, so a -0.0 comes back as +0.0.  The buffer is padded to a whole number of 4-float vector
+        elements, so any element count takes this route (a [1] or [2] slot at W = 3 as well)."""
         if self.size == 1:
             return t.unsqueeze(0)
-        if self.p2p is not None and t.dtype == torch.float32 and (t.numel() * self.size) % 4 == 0 \
-                and t.numel() * self.size * 4 <= self.p2p.half:
+        n = t.numel() * self.size
+        n4 = (n + 3) // 4 * 4
+        if self.p2p is not None and t.dtype == torch.float32 and n4 * 4 <= self.p2p.half:
             from ..ops.optim import fill_
 
-            out = torch.empty((self.size,) + tuple(t.shape), dtype=t.dtype, device=t.device)
-            fill_(out, 0.0)
+            flat = torch.empty(n4, dtype=t.dtype, device=t.device)
+            fill_(flat, 0.0)
+            out = flat[:n].view((self.size,) + tuple(t.shape))
             out[self.rank].copy_(t)
-            self.p2p.all_reduce_(out.view(-1))
+            self.p2p.all_reduce_(flat)
             return out
         out = torch.empty((self.size,) + tuple(t.shape), dtype=t.dtype, device=t.device)
         outs = list(out.unbind(0))
