@@ -1,7 +1,10 @@
 """In-process A/B of the layer-GEMM plans at a model's training shapes (every NT-layout GEMM the step
 runs: the forwards and the dgrads on transposed weights), interleaved rounds, with hipBLASLt
 (torch.matmul on the same bf16 operands) as a yardstick and a numerics check of every variant
-against an fp32 torch reference.
+against an fp32 torch reference.  The ``fp8 ...`` rows run the forwards on the e4m3 kernel (ops/fp8.py): ``kernel`` =
+the GEMM alone on operands quantised beforehand, ``+quant`` = with the activation's amax + quantise passes, as the
+step runs it (the weight is quantised once per step, outside these rows); compare them with the ``fwd`` row of
+the same layer.
 
     python benchmarks/gemm_layer_ab.py [--model gpt2-small] [--rounds 5] [--reps 30]
 
@@ -19,6 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_training_compare_jax_amd.ops import _native as N  # noqa: E402
+from distributed_training_compare_jax_amd.ops import fp8 as F8  # noqa: E402
 from distributed_training_compare_jax_amd.ops import gemm as G  # noqa: E402
 
 
@@ -92,6 +96,18 @@ def main():
         else:
             add(f"fwd {tag} [{M}x{n}x{k}]", fl, lambda x=x, w=w, b=b: G.linear(x, w, b),
                 lambda x=x, w=w, b=b: x.float() @ w.float().t() + b, lambda x=x, w=w: x @ w.t())
+        xq, wq = F8.quant_e4m3(x), F8.quant_e4m3(w)
+        ref8 = lambda x=x, w=w, b=b: x.float() @ w.float().t() + b  # noqa: E731
+        if tag == "fc1":
+            ref8 = lambda x=x, w=w, b=b: G.gelu_tanh(x.float() @ w.float().t() + b)  # noqa: E731
+            run8 = lambda xq, wq=wq, b=b: F8.linear_gelu_fp8(xq, wq, b)[1]  # noqa: E731
+        elif tag == "qkv":
+            run8 = lambda xq, wq=wq, b=b: F8.linear_fp8(xq, wq, b)  # noqa: E731
+        else:
+            run8 = lambda xq, wq=wq, b=b: F8.linear_fp8(xq, wq, b, out_dtype=torch.float32)  # noqa: E731
+        add(f"fp8 {tag} [{M}x{n}x{k}] kernel", fl, lambda xq=xq, run8=run8: run8(xq), ref8, lambda x=x, w=w: x @ w.t())
+        add(f"fp8 {tag} [{M}x{n}x{k}] +quant", fl, lambda x=x, run8=run8: run8(F8.quant_e4m3(x)), ref8,
+            lambda x=x, w=w: x @ w.t())
         dy, wt = r(M, n), w.t().contiguous()
         if tag in ("qkv", "fc1"):  # DTC_DGRAD_BF16: the input gradient stored bf16
             add(f"ntdgrad {tag} [{M}x{k}x{n}] bf16", fl, lambda dy=dy, wt=wt: G.linear(dy, wt),
@@ -144,7 +160,7 @@ def main():
             got = fn().float()
             err = ((got - want).norm() / want.norm()).item()
             print(f"check {name:36s} {vn:8s} rel err {err:.2e}", flush=True)
-            assert err < 1e-2, (name, vn, err)
+            assert err < (8e-2 if name.startswith("fp8") else 1e-2), (name, vn, err)  # fp8: the e4m3 quantisation
     res = {(c[0], v): [] for c in cases for v in list(variants) + ["hipBLASLt"]}
     for _ in range(a.rounds):
         for name, _, fn, _, blas in cases:

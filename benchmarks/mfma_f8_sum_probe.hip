@@ -1,0 +1,116 @@
+// How v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 operands, E8M0 scales 2^0) sums its 128 products: exact data
+// against the exact result.  One output element per case (row 0, column 0), one wave per case.
+//
+// Families (s = 1.875 * 2^-j, a product of 1.875 * 2^-a and 2^-b; X = a power of two):
+//   cancel   products +X, -X, s at k = 0, 1, pos; C = 0.  Exact result s.  What comes back shows how far below
+//            the largest product a small one is kept, and whether the cut rounds or truncates.
+//   acc      C = +X, products -X, s at k = 0, pos.  Exact result s: does the accumulator input join the same sum?
+//   tail     C = X, all 128 products s, exact result X + 128 s: the cut against C, and whether it truncates.
+//
+//   hipcc -O2 --offload-arch=gfx950 benchmarks/mfma_f8_sum_probe.hip -o mfma_f8_sum_probe && ./mfma_f8_sum_probe
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <vector>
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+static double e4m3_value(int c) {
+  const int s = c >> 7, e = (c >> 3) & 15, m = c & 7;
+  const double v = e == 0 ? ldexp(m / 8.0, -6) : ldexp(1.0 + m / 8.0, e - 7);
+  return s ? -v : v;
+}
+static uint8_t e4m3_code(double v) {
+  for (int c = 0; c < 256; ++c)
+    if ((c & 0x7f) != 0x7f && e4m3_value(c) == v && !(c == 0x80)) return (uint8_t)c;
+  fprintf(stderr, "not an e4m3 value: %g\n", v);
+  exit(2);
+}
+
+__global__ void probe(const uint8_t* A, const uint8_t* B, const float* C, float* D) {
+  const int cs = blockIdx.x, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+  i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (r == 0) {
+    const int* pa = (const int*)(A + cs * 128 + 32 * g);
+    const int* pb = (const int*)(B + cs * 128 + 32 * g);
+    for (int d = 0; d < 8; ++d) { a[d] = pa[d]; b[d] = pb[d]; }
+  }
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (lane == 0) acc[0] = C[cs];
+  acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+  // every lane stores: with the result used by lane 0 alone the compiler moves the MFMA and the scale operands'
+  // setup under that lane's EXEC mask, and the other lanes' scale registers then hold garbage
+  for (int q = 0; q < 4; ++q) D[cs * 256 + lane * 4 + q] = acc[q];
+}
+
+struct Case {
+  char name[64];
+  double a[128], b[128], c, exact;
+};
+
+int main() {
+  std::vector<Case> cases;
+  auto blank = [](const char* fmt, int x, int j, int pos) {
+    Case c{};
+    snprintf(c.name, sizeof c.name, fmt, x, j, pos);
+    return c;
+  };
+  // a product 1.875 * 2^-j from e4m3 factors: 1.875 * 2^-ja times 2^-jb, both in e4m3's normal range
+  auto small = [](int j, double& fa, double& fb) {
+    const int ja = j < -7 ? -7 : (j > 6 ? 6 : j), jb = j - ja;
+    fa = ldexp(1.875, -ja);
+    fb = ldexp(1.0, -jb);
+  };
+  const int xs[] = {16, 8, 0};
+  for (int x : xs)
+    for (int pos : {2, 40, 127})  // the block of X, another 32-element block, the last one
+      for (int j = x == 16 ? -8 : 0; j <= 12; ++j) {
+        Case c = blank("cancel X=2^%d s=1.875*2^-%d pos=%d", x, j, pos);
+        c.a[0] = ldexp(1.0, x / 2); c.b[0] = ldexp(1.0, x - x / 2);
+        c.a[1] = -c.a[0]; c.b[1] = c.b[0];
+        small(j, c.a[pos], c.b[pos]);
+        c.exact = ldexp(1.875, -j);
+        cases.push_back(c);
+      }
+  for (int x : xs)
+    for (int j = x == 16 ? -8 : 0; j <= 12; ++j) {
+      Case c = blank("acc    C=2^%d s=1.875*2^-%d pos=%d", x, j, 40);
+      c.c = ldexp(1.0, x);
+      c.a[0] = -ldexp(1.0, x / 2); c.b[0] = ldexp(1.0, x - x / 2);
+      small(j, c.a[40], c.b[40]);
+      c.exact = ldexp(1.875, -j);
+      cases.push_back(c);
+    }
+  for (int x : {16, 8})
+    for (int j = x == 16 ? -8 : 0; j <= 12; ++j) {
+      Case c = blank("tail   C=2^%d 128 x s=1.875*2^-%d (%d)", x, j, 0);
+      c.c = ldexp(1.0, x);
+      for (int k = 0; k < 128; ++k) small(j, c.a[k], c.b[k]);
+      c.exact = ldexp(1.0, x) + 128 * ldexp(1.875, -j);
+      cases.push_back(c);
+    }
+  const int n = (int)cases.size();
+  std::vector<uint8_t> ha(n * 128), hb(n * 128);
+  std::vector<float> hc(n), hd(n * 256);
+  for (int i = 0; i < n; ++i) {
+    for (int k = 0; k < 128; ++k) { ha[i * 128 + k] = e4m3_code(cases[i].a[k]); hb[i * 128 + k] = e4m3_code(cases[i].b[k]); }
+    hc[i] = (float)cases[i].c;
+  }
+  uint8_t *da, *db;
+  float *dc, *dd;
+  if (hipMalloc(&da, n * 128) != hipSuccess || hipMalloc(&db, n * 128) != hipSuccess ||
+      hipMalloc(&dc, n * 4) != hipSuccess || hipMalloc(&dd, n * 1024) != hipSuccess) return 2;
+  (void)hipMemcpy(da, ha.data(), n * 128, hipMemcpyHostToDevice);
+  (void)hipMemcpy(db, hb.data(), n * 128, hipMemcpyHostToDevice);
+  (void)hipMemcpy(dc, hc.data(), n * 4, hipMemcpyHostToDevice);
+  hipLaunchKernelGGL(probe, dim3(n), dim3(64), 0, 0, da, db, dc, dd);
+  if (hipMemcpy(hd.data(), dd, n * 1024, hipMemcpyDeviceToHost) != hipSuccess) return 3;
+  for (int i = 0; i < n; ++i) {
+    const double got = hd[i * 256], ex = cases[i].exact, rounded = (double)(float)ex;
+    printf("%-44s exact %.10g got %.10g diff %.6g%s\n", cases[i].name, ex, got, got - ex,
+           got == rounded ? "" : "   <-- not the exact result");
+  }
+  return 0;
+}

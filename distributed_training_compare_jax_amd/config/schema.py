@@ -120,6 +120,9 @@ class TrainConfig:
     pp_microbatches: int = 1
     # --- extensions ---
     dtype: str = "bf16"
+    # bf16 | fp8: the forward qkv / out_proj / fc1 / fc2 GEMMs.  fp8 = e4m3 operands with per-tensor power-of-two
+    # scales from the current tensor (ops/fp8.py); the backward, the lm_head and everything else stay as they are
+    fwd_gemm_dtype: str = "bf16"
     dp: Optional[int] = None
     tp: Optional[int] = None
     pp: Optional[int] = None

@@ -30,6 +30,7 @@ from ..ops import attention as A
 from ..ops import embedding as E
 from ..ops import gemm as G
 from ..ops import layernorm as LN
+from ..ops import fp8 as F8
 from ..ops import ln_fused as LF
 from ..ops import xent as X
 from ..ops.reduce import GradReducer
@@ -171,6 +172,18 @@ class GPTStage:
         # rows/tp rows per rank; the LN and row-parallel-bias grads are then per-rank partials (_sp_sum)
         self.sp = False
         self._sp_idx: Dict = {}
+        # FP8 forward (enable_fp8_forward): qkv / out_proj / fc1 / fc2 forwards on e4m3 operands
+        self.fp8 = False
+
+    def enable_fp8_forward(self):
+        """Run the four layer GEMMs of every block forward on the FP8 kernel (``ops/fp8.py``): each input (the
+        LayerNorm outputs, the attention output, gelu(u)) is quantised once with the scale of the current tensor
+        and multiplied with the FP8 weight mirror (``FlatParams.enable_fp8``).  The backward is unchanged: ``ctx``
+        holds the same unquantised tensors and the bf16 weights (a straight-through estimator).  tp == 1 only, and
+        not with the forward LayerNorm fusion (the engine refuses those settings)."""
+        assert self.tp.size == 1 and not self._fuse_fwd and not self.sp
+        self.flat.enable_fp8([f"h.{l}.{n}.w" for l in self.layout.layers for n in ("qkv", "out", "fc1", "fc2")])
+        self.fp8 = True
 
     def set_wgrad_group(self, layers: int):
         """Defer weight gradients to grouped launches of ``layers`` consecutive layers (0 = all layers of
@@ -353,9 +366,14 @@ class GPTStage:
         if pre is None:
             pre = LN.layernorm_fwd(x, f.p(p + "ln1.g"), f.p(p + "ln1.b"), self.eps, self.act_dtype)
         y1, mu1, rs1 = pre
-        qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
+        fp8 = self.fp8  # the four layer GEMMs on e4m3 operands (enable_fp8_forward); ctx keeps the same tensors
+        if fp8:
+            qkv = F8.linear_fp8(F8.quant_e4m3(y1), f.w8(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=self.act_dtype)
+        else:
+            qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
         o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local)
         o = o.view(batch * T, -1)
+        oq = F8.quant_e4m3(o) if fp8 else None
         if self._fuse_fwd:
             x2, (y2, mu2, rs2) = LF.linear_resid_ln(o, f.w(p + "out.w"), f.p(p + "out.b"), x, f.p(p + "ln2.g"),
                                                     f.p(p + "ln2.b"), self.eps, self.ln_sync, self._ln_site(l, 0, False))
@@ -365,14 +383,22 @@ class GPTStage:
         elif tp.size == 1 and _ADD_LN:
             # residual add in the LayerNorm pass (the GEMM stores o·Wᵀ + b; its epilogue skips the fp32
             # residual read) -- same fp32 arithmetic, (acc + b) + x
-            x2, (y2, mu2, rs2) = LN.add_layernorm_fwd(G.linear(o, f.w(p + "out.w"), f.p(p + "out.b"),
-                                                               out_dtype=self._branch_dtype), x,
-                                                      f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, self.act_dtype)
+            br = (F8.linear_fp8(oq, f.w8(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype) if fp8 else
+                  G.linear(o, f.w(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype))
+            x2, (y2, mu2, rs2) = LN.add_layernorm_fwd(br, x, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps,
+                                                      self.act_dtype)
         else:
-            x2 = G.linear_resid(o, f.w(p + "out.w"), f.p(p + "out.b") if lead else None, x if lead else None)
+            if fp8:
+                x2 = F8.linear_resid_fp8(oq, f.w8(p + "out.w"), f.p(p + "out.b"), x)
+            else:
+                x2 = G.linear_resid(o, f.w(p + "out.w"), f.p(p + "out.b") if lead else None, x if lead else None)
             tp.all_reduce_(x2)
             y2, mu2, rs2 = LN.layernorm_fwd(x2, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, self.act_dtype)
-        u, gact = G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))  # u = gelu'(pre-activation)
+        if fp8:
+            u, gact = F8.linear_gelu_fp8(F8.quant_e4m3(y2), f.w8(p + "fc1.w"), f.p(p + "fc1.b"), out_dtype=self.act_dtype)
+            gq = F8.quant_e4m3(gact)
+        else:
+            u, gact = G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))  # u = gelu'(pre-activation)
         # the LayerNorm that reads x3: the next layer's ln1, or the final one after the last layer
         nxt = f"h.{l + 1}.ln1" if (l + 1) in self.layout.layers else ("lnf" if self.layout.has_head else None)
         if self._fuse_fwd and nxt is not None:
@@ -380,12 +406,14 @@ class GPTStage:
                                               f.p(nxt + ".b"), self.eps, self.ln_sync, self._ln_site(l, 1, False))
             ctx[("ln1", l + 1) if nxt != "lnf" else "lnf_pre"] = pre_next
         elif tp.size == 1 and _ADD_LN and nxt is not None and not self.tp_bf16:
-            x3, pre_next = LN.add_layernorm_fwd(G.linear(gact, f.w(p + "fc2.w"), f.p(p + "fc2.b"),
-                                                         out_dtype=self._branch_dtype), x2,
-                                                f.p(nxt + ".g"), f.p(nxt + ".b"), self.eps, self.act_dtype)
+            br = (F8.linear_fp8(gq, f.w8(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype) if fp8 else
+                  G.linear(gact, f.w(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype))
+            x3, pre_next = LN.add_layernorm_fwd(br, x2, f.p(nxt + ".g"), f.p(nxt + ".b"), self.eps, self.act_dtype)
             ctx[("ln1", l + 1) if nxt != "lnf" else "lnf_pre"] = pre_next
         elif self.tp_bf16:
             x3 = self._row_parallel(gact, p + "fc2.w", resid=x2, bias=f.p(p + "fc2.b"))
+        elif fp8:
+            x3 = F8.linear_resid_fp8(gq, f.w8(p + "fc2.w"), f.p(p + "fc2.b"), x2)
         else:
             x3 = G.linear_resid(gact, f.w(p + "fc2.w"), f.p(p + "fc2.b") if lead else None, x2 if lead else None)
             tp.all_reduce_(x3)

@@ -22,9 +22,44 @@ def _gelu_tanh(x):
     return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
 
 
+class _FakeQuantLinear(torch.autograd.Function):
+    """``deq(Q(x)) · deq(Q(bf16(W)))ᵀ`` with the e4m3 quantiser of ``ops/fp8.py``; the backward is the plain
+    matmul's on the unquantised operands (straight-through)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bf16_inputs, sink):
+        from ..ops import fp8 as F8
+
+        ctx.save_for_backward(x, w)
+        x2 = x.reshape(-1, x.shape[-1])
+        if bf16_inputs:
+            x2 = x2.to(torch.bfloat16).float()
+        if sink is not None:
+            sink.append(x2.detach().clone())
+        xq = F8.dequant(F8.quant_e4m3(x2.contiguous()))
+        wq = F8.dequant(F8.quant_e4m3(w.detach().to(torch.bfloat16).contiguous()))
+        return (xq @ wq.t()).view(*x.shape[:-1], w.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g2 = g.reshape(-1, g.shape[-1])
+        return g @ w, g2.t() @ x.reshape(-1, x.shape[-1]), None, None
+
+
 def oracle_loss(cfg: ModelConfig, params: dict, ids: torch.Tensor, labels: torch.Tensor, seed: int, step: int,
-                row0: int = 0) -> torch.Tensor:
-    """params: name → fp32 tensor (full shapes, [out,in] Dense layout), requires_grad allowed."""
+                row0: int = 0, fake_quant: bool = False, quant_bf16_inputs: bool = False,
+                quant_inputs: list = None) -> torch.Tensor:
+    """params: name → fp32 tensor (full shapes, [out,in] Dense layout), requires_grad allowed.
+
+    ``fake_quant`` (default off): the four layer GEMMs of every block (qkv, out_proj, fc1, fc2) run as
+    :class:`_FakeQuantLinear`, the statement of ``TrainConfig.fwd_gemm_dtype: fp8``; the lm_head stays as it is.
+    ``quant_bf16_inputs`` rounds each quantiser's activation input to bf16 first (what the bf16 engine feeds it);
+    ``quant_inputs``: a list that collects every quantiser's activation input, in call order."""
+    if fake_quant:
+        mm = lambda a, w: _FakeQuantLinear.apply(a, w, quant_bf16_inputs, quant_inputs)  # noqa: E731
+    else:
+        mm = lambda a, w: a @ w.t()  # noqa: E731
     B, T = ids.shape
     D, H = cfg.d_model, cfg.n_heads
     hd = D // H
@@ -39,16 +74,16 @@ def oracle_loss(cfg: ModelConfig, params: dict, ids: torch.Tensor, labels: torch
         p = lambda n: params[f"h.{l}.{n}"]  # noqa: E731
         r = h
         x = F.layer_norm(h, (D,), p("ln1.g"), p("ln1.b"), eps)
-        qkv = x @ p("qkv.w").t() + p("qkv.b")
+        qkv = mm(x, p("qkv.w")) + p("qkv.b")
         q, k, v = qkv.view(B, T, 3, H, hd).unbind(2)
         s = torch.einsum("bthd,bshd->bhts", q, k) * hd ** -0.5 + add_mask
         a = torch.softmax(s, -1)
         o = torch.einsum("bhts,bshd->bthd", a, v).reshape(B, T, D)
-        h = o @ p("out.w").t() + p("out.b") + r
+        h = mm(o, p("out.w")) + p("out.b") + r
         r = h
         x = F.layer_norm(h, (D,), p("ln2.g"), p("ln2.b"), eps)
-        x = _gelu_tanh(x @ p("fc1.w").t() + p("fc1.b"))
-        h = x @ p("fc2.w").t() + p("fc2.b") + r
+        x = _gelu_tanh(mm(x, p("fc1.w")) + p("fc1.b"))
+        h = mm(x, p("fc2.w")) + p("fc2.b") + r
     x = F.layer_norm(h, (D,), params["lnf.g"], params["lnf.b"], eps)
     V = cfg.vocab_size
     logits = x @ params["lm_head.w"][:V].t() + params["lm_head.b"][:V]

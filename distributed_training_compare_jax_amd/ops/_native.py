@@ -192,6 +192,14 @@ def _declare(lib):
         "dtc_attn_f32_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, f, vp, l, vp], i),
         "dtc_attn_f32_bwd_workspace_bytes": ([i, i, i, i], l),
         "dtc_ce_bwd_f32": ([vp, l, vp, vp, i, i, i, i, f, vp, vp], i),
+        # FP8 (e4m3) forward path (csrc/gemm_fp8.hip); the argument structs live in ops/fp8.py
+        "dtc_quant_e4m3_tasks": ([vp, vp, l, vp], i),
+        "dtc_qt_max": ([], i),
+        "dtc_qt_task_bytes": ([], i),
+        "dtc_qt_batch_bytes": ([], i),
+        "dtc_gemm_fp8": ([vp, vp], i),
+        "dtc_gemm_fp8_set_tile_m": ([i], i),
+        "dtc_gemm_fp8_last_launch": ([ctypes.POINTER(c_int)], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)

@@ -76,6 +76,8 @@ class FlatParams:
         # transposed compute mirror (enable_transposed): name -> (slot, [in, out] bf16 view)
         self.mirror_t: Dict[str, Tuple[Slot, torch.Tensor]] = {}
         self._mirror_t_buf = None
+        # FP8 weight mirror (enable_fp8): name -> (slot, ops.fp8.Fp8Tensor), rebuilt wherever the bf16 mirror is
+        self.mirror_fp8: Dict[str, Tuple[Slot, object]] = {}
 
     # -- init -----------------------------------------------------------------
     def init_canonical(self, seed: int):
@@ -91,6 +93,7 @@ class FlatParams:
 
             cast_to_bf16(self.params[: self.n_mirror], self.mirror[: self.n_mirror])
             self.refresh_transposed()
+        self.refresh_fp8()
 
     # -- transposed mirror --------------------------------------------------------
     def enable_transposed(self, names: List[str]):
@@ -125,6 +128,49 @@ class FlatParams:
         """[(flat offset, rows, cols, W^T)] of the transposed-mirror weights inside flat[lo:hi]."""
         return [(sl.offset, sl.shape[0], sl.shape[1], t) for sl, t in self.mirror_t.values()
                 if sl.offset >= lo and sl.offset + sl.numel <= hi]
+
+    # -- FP8 weight mirror ------------------------------------------------------------
+    def enable_fp8(self, names: List[str]):
+        """Keep an e4m3 copy (bytes + per-tensor power-of-two scale, ``ops/fp8.py``) of these 2-D mirrored weights:
+        ``quant_e4m3`` of the bf16 mirror (of the master rounded to bf16 where no mirror is kept).  Rebuilt by
+        :meth:`refresh_fp8` wherever the bf16 mirror is rebuilt or written; not part of a checkpoint."""
+        from ..ops import fp8 as F8
+
+        names = [n for n in names if n in self.slots and self.slots[n].spec.mirror and len(self.slots[n].shape) == 2]
+        if not names:
+            return
+        names.sort(key=lambda n: self.slots[n].offset)  # a flat range then holds a run of consecutive entries
+        self._fp8_state = F8.new_state(len(names), self.device)
+        self._fp8_buf = torch.zeros(sum(self.slots[n].numel for n in names), dtype=torch.uint8, device=self.device)
+        off = 0
+        for i, n in enumerate(names):
+            sl = self.slots[n]
+            q = self._fp8_buf[off:off + sl.numel].view(sl.shape)
+            self.mirror_fp8[n] = (sl, F8._views(q, self._fp8_state[i]))
+            off += sl.numel
+        self.refresh_fp8()
+
+    def refresh_fp8(self, lo: int = 0, hi: int = None):
+        """Requantise the FP8 copies of the weights inside flat[lo:hi] (one batched quantiser call)."""
+        if not self.mirror_fp8:
+            return
+        from ..ops import fp8 as F8
+
+        hi = self.numel if hi is None else hi
+        idx = [i for i, (sl, _) in enumerate(self.mirror_fp8.values()) if sl.offset >= lo and sl.offset + sl.numel <= hi]
+        if not idx:
+            return
+        i0, i1 = idx[0], idx[-1] + 1  # entries are sorted by offset: the ones inside a range are consecutive
+        ent = list(self.mirror_fp8.items())[i0:i1]
+        src = [self.w(n) if self.use_mirror else self.p(n).to(torch.bfloat16) for n, _ in ent]
+        F8.quant_e4m3_batch(src, [t.q for _, (_, t) in ent], self._fp8_state[i0:i1])
+
+    def w8(self, name: str):
+        """The e4m3 copy of a weight (``ops.fp8.Fp8Tensor``); raises when none is kept."""
+        e = self.mirror_fp8.get(name)
+        if e is None:
+            raise KeyError(f"no FP8 mirror of {name!r} (FlatParams.enable_fp8)")
+        return e[1]
 
     def wt(self, name: str):
         """Transposed bf16 view ``[in, out]`` of a weight, or None when not kept."""

@@ -64,6 +64,24 @@ class Engine:
             if mult != model_cfg.vocab_pad_multiple:
                 model_cfg = replace(model_cfg, vocab_pad_multiple=mult)
                 self.mcfg = model_cfg
+        # FP8 forward GEMMs (models/gpt.py enable_fp8_forward): what it does not cover is refused here, by name
+        if train_cfg.fwd_gemm_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"fwd_gemm_dtype={train_cfg.fwd_gemm_dtype!r}: expected 'bf16' or 'fp8'")
+        if train_cfg.fwd_gemm_dtype == "fp8":
+            why = None
+            if train_cfg.dtype == "fp32":
+                why = "dtype=fp32 (the exact-fp32 parity mode has no reduced-precision GEMMs)"
+            elif tp > 1:
+                why = f"tp={tp} (the row-parallel and sequence-parallel forwards are not covered; use tp = 1)"
+            elif train_cfg.defer_optimizer:
+                why = "defer_optimizer=true (the FP8 weight mirror is rebuilt by the end-of-step update)"
+            elif dinfo.device.type == "cuda" and int(os.environ.get("DTC_LN_FUSE", "2")) & 1:
+                why = "DTC_LN_FUSE with bit 1 set (the forward LayerNorm fusion runs its own bf16 GEMM)"
+            elif model_cfg.d_model % 128 or model_cfg.d_ff % 128:
+                why = (f"d_model={model_cfg.d_model}, d_ff={model_cfg.d_ff} (the FP8 GEMM's k-step is 128: both must "
+                       "be multiples of 128)")
+            if why:
+                raise ValueError(f"fwd_gemm_dtype=fp8 cannot be combined with {why}")
         rehearse = bool(train_cfg.dp_comm_rehearsal and dp == 1 and dist.is_available() and dist.is_initialized())
         self.mesh: Mesh = build_mesh(dinfo.rank, dinfo.world, dp, tp, pp, dp_group_always=rehearse)
         m = self.mesh
@@ -333,6 +351,8 @@ class Engine:
             has_wt = len(self.layout.layers) > 0 and self.flat.wt(f"h.{self.layout.layers[0]}.fc1.w") is not None
             self.stage.enable_ln_fusion(self.b_local * T, self.opt.step_t, fwd=bool(lnf & 1),
                                         bwd=bool(lnf & 2) and has_wt)
+        if train_cfg.fwd_gemm_dtype == "fp8":
+            self.stage.enable_fp8_forward()
         if on_gpu:
             self._reserve_workspaces()
 
