@@ -9,7 +9,9 @@ that GSPMD shards, ``train/create_train_step.py:31``).  The backward regenerates
 replayed from a hipGraph.
 
 GPU path: ``csrc/elementwise.hip``.  The CPU path below reproduces the kernel's Philox bits
-exactly (tested).
+and its keep decision exactly (tested): an element is kept when its draw ``u >= int(float32(p) · 2^32)``, with
+``p`` rounded to float32 first as the kernel receives it.  (Until this was fixed the CPU threshold came from the
+double ``p``, 7 below the kernel's at p = 0.1, so about 1.6e-9 of the elements were kept here and dropped there.)
 """
 
 from __future__ import annotations
@@ -43,6 +45,12 @@ def philox4x32(c0, c1, c2, c3, k0: int, k1: int, rounds: int = 10):
     return c0, c1, c2, c3
 
 
+def drop_threshold(p: float) -> int:
+    """Draws below this are dropped (``drop_threshold`` in ``csrc/elementwise.hip``): the kernel receives ``p`` as
+    a C float, so ``p`` is rounded to float32 before it is scaled (0.1 -> 429496736, not 429496729)."""
+    return min(int(float(np.float32(p)) * 4294967296.0), 0xFFFFFFFF)
+
+
 def dropout_keep_mask(n_tokens: int, D: int, token0: int, p: float, seed: int, step: int) -> torch.Tensor:
     """Keep-mask [n_tokens, D] (bool) for global tokens [token0, token0+n_tokens)."""
     assert D % 4 == 0
@@ -50,8 +58,7 @@ def dropout_keep_mask(n_tokens: int, D: int, token0: int, p: float, seed: int, s
     groups = np.arange(e0 // 4, (e0 + n_tokens * D) // 4, dtype=np.uint64)
     r = philox4x32(groups & _U32, groups >> np.uint64(32), 0, 0, seed, step)
     u = np.stack(r, axis=1).reshape(-1)  # element e = 4*group + lane
-    thr = np.uint64(min(int(p * 4294967296.0), 0xFFFFFFFF))
-    keep = u >= thr
+    keep = u >= np.uint64(drop_threshold(p))
     return torch.from_numpy(keep.reshape(n_tokens, D))
 
 

@@ -163,6 +163,25 @@ def test_philox_known_answer_and_rate():
     assert torch.equal(sub, keep[37:137])
 
 
+def test_dropout_threshold_is_the_kernels_float32_threshold():
+    """The kernel gets ``p`` as a C float: its threshold is ``int(float32(p) · 2^32)`` (429496736 at p = 0.1), not
+    ``int(p · 2^32)`` (429496729).  Seed 1234, step 7, counter group 16500423, lane 2 draws u = 429496729, inside
+    that window (found by a CPU search over the counter with ``E.philox4x32``): token 257819 * 4, channel 30 at
+    D = 64 is dropped by the kernel, so the CPU mask must drop it as well."""
+    u = int(E.philox4x32(16500423, 0, 0, 0, 1234, 7)[2])
+    assert u == 429496729 and int(0.1 * 2 ** 32) <= u < int(float(np.float32(0.1)) * 2 ** 32) == 429496736
+    keep = E.dropout_keep_mask(4, 64, 257819 * 4, 0.1, 1234, 7)
+    assert not bool(keep[0, 30])
+    n_tok, D, tok0 = 64, 64, 257819 * 4 - 5
+    groups = np.arange(tok0 * D // 4, (tok0 + n_tok) * D // 4, dtype=np.uint64)
+    draw = np.stack(E.philox4x32(groups & np.uint64(0xFFFFFFFF), groups >> np.uint64(32), 0, 0, 1234, 7), axis=1)
+    for p in (0.05, 0.1, 0.2, 0.3, 0.5):
+        thr = int(float(np.float32(p)) * 2 ** 32)
+        want = torch.from_numpy((draw.reshape(n_tok, D) >= np.uint64(thr)))
+        assert torch.equal(E.dropout_keep_mask(n_tok, D, tok0, p, 1234, 7), want), p
+    assert not bool(E.dropout_keep_mask(n_tok, D, tok0, 0.1, 1234, 7)[5, 30])
+
+
 @pytest.mark.parametrize("dropout", [0.0, 0.1])
 def test_explicit_backward_matches_autograd(dropout):
     mc = model_config_from_preset("tiny", vocab_size=1000, dropout=dropout)
