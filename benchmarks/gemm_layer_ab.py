@@ -4,7 +4,8 @@ runs: the forwards and the dgrads on transposed weights), interleaved rounds, wi
 against an fp32 torch reference.  The ``fp8 ...`` rows run the forwards on the e4m3 kernel (ops/fp8.py): ``kernel`` =
 the GEMM alone on operands quantised beforehand, ``+quant`` = with the activation's amax + quantise passes, as the
 step runs it (the weight is quantised once per step, outside these rows); compare them with the ``fwd`` row of
-the same layer.
+the same layer.  The ``mxfp8 ...`` rows do the same for the block-scaled kernel (ops/mxfp8.py) and time the LayerNorm
+forward without and with its fused MX output.
 
     python benchmarks/gemm_layer_ab.py [--model gpt2-small] [--rounds 5] [--reps 30]
 
@@ -24,6 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_training_compare_jax_amd.ops import _native as N  # noqa: E402
 from distributed_training_compare_jax_amd.ops import fp8 as F8  # noqa: E402
 from distributed_training_compare_jax_amd.ops import gemm as G  # noqa: E402
+from distributed_training_compare_jax_amd.ops import layernorm as LN  # noqa: E402
+from distributed_training_compare_jax_amd.ops import mxfp8 as MX  # noqa: E402
 
 
 def graph_time(fn, reps, pre=None):
@@ -108,6 +111,30 @@ def main():
         add(f"fp8 {tag} [{M}x{n}x{k}] kernel", fl, lambda xq=xq, run8=run8: run8(xq), ref8, lambda x=x, w=w: x @ w.t())
         add(f"fp8 {tag} [{M}x{n}x{k}] +quant", fl, lambda x=x, run8=run8: run8(F8.quant_e4m3(x)), ref8,
             lambda x=x, w=w: x @ w.t())
+        # MXFP8 (ops/mxfp8.py): ``kernel`` = the GEMM alone as the step runs it (fc1 with the fused MX output of
+        # gelu(u)), ``+quant1`` = with the one-pass stand-alone quantiser of its activation in front: what the step
+        # pays for out_proj (its input is the attention output), and for every GEMM under DTC_MX_FUSE=0
+        xm, wm = MX.quant_mxfp8(x), MX.quant_mxfp8(w)
+        if tag == "fc1":
+            runm = lambda xm, wm=wm, b=b: MX.linear_gelu_mxfp8(xm, wm, b, quant_out=True)[1]  # noqa: E731
+            add(f"mxfp8 {tag} [{M}x{n}x{k}] gelu only", fl, lambda xm=xm, wm=wm, b=b: MX.linear_gelu_mxfp8(xm, wm, b)[1],
+                ref8, lambda x=x, w=w: x @ w.t())
+        elif tag == "qkv":
+            runm = lambda xm, wm=wm, b=b: MX.linear_mxfp8(xm, wm, b)  # noqa: E731
+        else:
+            runm = lambda xm, wm=wm, b=b: MX.linear_mxfp8(xm, wm, b, out_dtype=torch.float32)  # noqa: E731
+        add(f"mxfp8 {tag} [{M}x{n}x{k}] kernel", fl, lambda xm=xm, runm=runm: runm(xm), ref8, lambda x=x, w=w: x @ w.t())
+        add(f"mxfp8 {tag} [{M}x{n}x{k}] +quant1", fl, lambda x=x, runm=runm: runm(MX.quant_mxfp8(x)), ref8,
+            lambda x=x, w=w: x @ w.t())
+        if tag == "qkv":  # the LayerNorm forward that produces the qkv / fc1 input, without and with its MX output
+            h = torch.randn(M, k, device=dev, generator=g)
+            gam, bet = torch.rand(k, device=dev, generator=g) + 0.5, torch.randn(k, device=dev, generator=g) * 0.1
+            lnref = lambda h=h, gam=gam, bet=bet: torch.nn.functional.layer_norm(h, (h.shape[1],), gam, bet, 1e-6)  # noqa: E731
+            lnb = 3.0 * M * k  # not a GEMM: the TF/s column of these two rows means nothing
+            add(f"ln fwd [{M}x{k}] plain", lnb, lambda h=h, gam=gam, bet=bet: LN.layernorm_fwd(h, gam, bet, 1e-6, torch.bfloat16)[0],
+                lnref, lnref)
+            add(f"ln fwd [{M}x{k}] +mx out", lnb,
+                lambda h=h, gam=gam, bet=bet: MX.layernorm_fwd_mx(h, gam, bet, 1e-6, torch.bfloat16)[0][0], lnref, lnref)
         dy, wt = r(M, n), w.t().contiguous()
         if tag in ("qkv", "fc1"):  # DTC_DGRAD_BF16: the input gradient stored bf16
             add(f"ntdgrad {tag} [{M}x{k}x{n}] bf16", fl, lambda dy=dy, wt=wt: G.linear(dy, wt),
@@ -160,7 +187,7 @@ def main():
             got = fn().float()
             err = ((got - want).norm() / want.norm()).item()
             print(f"check {name:36s} {vn:8s} rel err {err:.2e}", flush=True)
-            assert err < (8e-2 if name.startswith("fp8") else 1e-2), (name, vn, err)  # fp8: the e4m3 quantisation
+            assert err < (8e-2 if name.startswith(("fp8", "mxfp8")) else 1e-2), (name, vn, err)  # the e4m3 quantisation
     res = {(c[0], v): [] for c in cases for v in list(variants) + ["hipBLASLt"]}
     for _ in range(a.rounds):
         for name, _, fn, _, blas in cases:

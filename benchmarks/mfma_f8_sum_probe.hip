@@ -1,11 +1,19 @@
-// How v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 operands, E8M0 scales 2^0) sums its 128 products: exact data
-// against the exact result.  One output element per case (row 0, column 0), one wave per case.
+// How v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 operands; E8M0 scales 2^0, unequal block scales in the mx family)
+// sums its 128 products: exact data against the exact result.  One output element per case (row 0, column 0), one
+// wave per case.  pos = 32 g + j is byte j of lane group g; the instruction's own k of that byte is 16 g + j for
+// j < 16 and 64 + 16 g + (j - 16) above (mfma_f8_map_probe.hip), so pos 0, 1, 2 share one 16-byte piece, pos 20 is
+// the same lane's other piece, pos 40 is another lane of the same 32-element scale block.
 //
 // Families (s = 1.875 * 2^-j, a product of 1.875 * 2^-a and 2^-b; X = a power of two):
-//   cancel   products +X, -X, s at k = 0, 1, pos; C = 0.  Exact result s.  What comes back shows how far below
+//   cancel   products +X, -X, s at pos = 0, 1, pos; C = 0.  Exact result s.  What comes back shows how far below
 //            the largest product a small one is kept, and whether the cut rounds or truncates.
 //   acc      C = +X, products -X, s at k = 0, pos.  Exact result s: does the accumulator input join the same sum?
 //   tail     C = X, all 128 products s, exact result X + 128 s: the cut against C, and whether it truncates.
+//   mx       the cancel family with unequal E8M0 block scales, placed by the instruction's own k (lane group b
+//            supplies the scale byte of block b = k / 32, replicated into the four bytes of the scale register):
+//            +X, -X at k = 0, 1 in block 0, which carries 2^u on A; s at k, whose block (if not block 0) carries
+//            2^-w.  Exact result s 2^u in block 0 and s 2^-w elsewhere.  Does a block with a larger scale cut the
+//            products of another block, and is the cut inside a piece still 13 bits below its own largest product?
 //
 //   hipcc -O2 --offload-arch=gfx950 benchmarks/mfma_f8_sum_probe.hip -o mfma_f8_sum_probe && ./mfma_f8_sum_probe
 #include <hip/hip_runtime.h>
@@ -29,7 +37,8 @@ static uint8_t e4m3_code(double v) {
   exit(2);
 }
 
-__global__ void probe(const uint8_t* A, const uint8_t* B, const float* C, float* D) {
+__global__ void probe(const uint8_t* A, const uint8_t* B, const float* C, float* D, const uint8_t* SA,
+                      const uint8_t* SB) {
   const int cs = blockIdx.x, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
   i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
   if (r == 0) {
@@ -39,7 +48,8 @@ __global__ void probe(const uint8_t* A, const uint8_t* B, const float* C, float*
   }
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (lane == 0) acc[0] = C[cs];
-  acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+  const int sa = SA[cs * 4 + g] * 0x01010101, sb = SB[cs * 4 + g] * 0x01010101;  // this lane's own block
+  acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 0, 0, 0, sa, 0, sb);
   // every lane stores: with the result used by lane 0 alone the compiler moves the MFMA and the scale operands'
   // setup under that lane's EXEC mask, and the other lanes' scale registers then hold garbage
   for (int q = 0; q < 4; ++q) D[cs * 256 + lane * 4 + q] = acc[q];
@@ -48,6 +58,7 @@ __global__ void probe(const uint8_t* A, const uint8_t* B, const float* C, float*
 struct Case {
   char name[64];
   double a[128], b[128], c, exact;
+  int sa[4], sb[4];  // E8M0 exponent of each 32-element block's scale, per operand (0 = 2^0)
 };
 
 int main() {
@@ -65,7 +76,7 @@ int main() {
   };
   const int xs[] = {16, 8, 0};
   for (int x : xs)
-    for (int pos : {2, 40, 127})  // the block of X, another 32-element block, the last one
+    for (int pos : {2, 20, 40, 127})  // X's 16-byte piece, its lane's other piece, another lane, the last lane
       for (int j = x == 16 ? -8 : 0; j <= 12; ++j) {
         Case c = blank("cancel X=2^%d s=1.875*2^-%d pos=%d", x, j, pos);
         c.a[0] = ldexp(1.0, x / 2); c.b[0] = ldexp(1.0, x - x / 2);
@@ -91,21 +102,53 @@ int main() {
       c.exact = ldexp(1.0, x) + 128 * ldexp(1.875, -j);
       cases.push_back(c);
     }
+  // the instruction's own k of an operand byte (benchmarks/mfma_f8_map_probe.hip, scale block probe): byte j of lane
+  // group g is k = 16 g + j for j < 16 and k = 64 + 16 g + (j - 16) above; at(k) is the position g * 32 + j of k
+  auto at = [](int k) { return 32 * ((k & 63) >> 4) + 16 * (k >> 6) + (k & 15); };
+  for (int x : {16, 0})
+    for (int k : {2, 20, 40, 68, 127})  // X's 16-byte piece; X's scale block, another lane; other blocks (68: X's lane)
+      for (int u : {5, 0})
+        for (int w : {0, 5}) {
+          if ((u == 0 && w == 0) || (k < 32 && w)) continue;
+          for (int j = 4; j <= 12; ++j) {
+            Case c{};
+            snprintf(c.name, sizeof c.name, "mx X=2^%d*2^%d s=1.875*2^-%d*2^%d k=%d", x, u, j, k < 32 ? u : -w, k);
+            c.a[at(0)] = ldexp(1.0, x / 2); c.b[at(0)] = ldexp(1.0, x - x / 2);
+            c.a[at(1)] = -c.a[at(0)]; c.b[at(1)] = c.b[at(0)];
+            small(j, c.a[at(k)], c.b[at(k)]);
+            c.sa[0] = u;
+            if (k >= 32) c.sa[k / 32] = -w;
+            c.exact = ldexp(1.875, -j + (k < 32 ? u : -w));
+            cases.push_back(c);
+          }
+        }
+  {  // A and B scales of one block both set, distinct: the product carries 2^(3 - 2) (a swapped or dropped scale shows)
+    Case c{};
+    snprintf(c.name, sizeof c.name, "mx both: a=1.5*2^3 b=1.25*2^-2 k=70");
+    c.a[at(70)] = 1.5; c.b[at(70)] = 1.25; c.sa[2] = 3; c.sb[2] = -2; c.sa[1] = 7; c.sb[3] = -7; c.sa[0] = 5; c.sb[0] = 4;
+    c.exact = 1.5 * 1.25 * 2.0;
+    cases.push_back(c);
+  }
   const int n = (int)cases.size();
   std::vector<uint8_t> ha(n * 128), hb(n * 128);
   std::vector<float> hc(n), hd(n * 256);
+  std::vector<uint8_t> hsa(n * 4), hsb(n * 4);
   for (int i = 0; i < n; ++i) {
     for (int k = 0; k < 128; ++k) { ha[i * 128 + k] = e4m3_code(cases[i].a[k]); hb[i * 128 + k] = e4m3_code(cases[i].b[k]); }
     hc[i] = (float)cases[i].c;
+    for (int g = 0; g < 4; ++g) { hsa[i * 4 + g] = (uint8_t)(127 + cases[i].sa[g]); hsb[i * 4 + g] = (uint8_t)(127 + cases[i].sb[g]); }
   }
-  uint8_t *da, *db;
+  uint8_t *da, *db, *dsa, *dsb;
   float *dc, *dd;
   if (hipMalloc(&da, n * 128) != hipSuccess || hipMalloc(&db, n * 128) != hipSuccess ||
       hipMalloc(&dc, n * 4) != hipSuccess || hipMalloc(&dd, n * 1024) != hipSuccess) return 2;
+  if (hipMalloc(&dsa, n * 4) != hipSuccess || hipMalloc(&dsb, n * 4) != hipSuccess) return 2;
+  (void)hipMemcpy(dsa, hsa.data(), n * 4, hipMemcpyHostToDevice);
+  (void)hipMemcpy(dsb, hsb.data(), n * 4, hipMemcpyHostToDevice);
   (void)hipMemcpy(da, ha.data(), n * 128, hipMemcpyHostToDevice);
   (void)hipMemcpy(db, hb.data(), n * 128, hipMemcpyHostToDevice);
   (void)hipMemcpy(dc, hc.data(), n * 4, hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(probe, dim3(n), dim3(64), 0, 0, da, db, dc, dd);
+  hipLaunchKernelGGL(probe, dim3(n), dim3(64), 0, 0, da, db, dc, dd, dsa, dsb);
   if (hipMemcpy(hd.data(), dd, n * 1024, hipMemcpyDeviceToHost) != hipSuccess) return 3;
   for (int i = 0; i < n; ++i) {
     const double got = hd[i * 256], ex = cases[i].exact, rounded = (double)(float)ex;

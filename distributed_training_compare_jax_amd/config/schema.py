@@ -120,8 +120,10 @@ class TrainConfig:
     pp_microbatches: int = 1
     # --- extensions ---
     dtype: str = "bf16"
-    # bf16 | fp8: the forward qkv / out_proj / fc1 / fc2 GEMMs.  fp8 = e4m3 operands with per-tensor power-of-two
-    # scales from the current tensor (ops/fp8.py); the backward, the lm_head and everything else stay as they are
+    # bf16 | fp8 | mxfp8: the forward qkv / out_proj / fc1 / fc2 GEMMs.  fp8 = e4m3 operands with per-tensor
+    # power-of-two scales from the current tensor (ops/fp8.py); mxfp8 = e4m3 operands with one power-of-two scale per
+    # 32 elements of k (OCP microscaling, ops/mxfp8.py), quantised inside the LayerNorm and GELU kernels that produce
+    # them; the backward, the lm_head and everything else stay as they are
     fwd_gemm_dtype: str = "bf16"
     dp: Optional[int] = None
     tp: Optional[int] = None

@@ -7,6 +7,7 @@
 //   GEMM        C[M,N] = (Aq[M,K] . Bq[N,K]^T) * (1/sa) * (1/sb) (+ epilogue), both operands K-major e4m3,
 //               fp32 accumulation; K % 128 == 0, N % 16 == 0, any M >= 1.
 #include "common.h"
+#include "fp8_quant.h"
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
@@ -37,6 +38,7 @@ __device__ __forceinline__ int quant_task_of(const QuantBatch& b, int blk) {
 // The scale from amax's bit pattern.  e = biased exponent - 127; amax * 2^(8-e) = 256 * mantissa is above 448
 // exactly when the mantissa is above 1.75 (fraction bits > 0x600000).  The exponent of s is clamped to
 // [-126, 126] so that s and 1/s are normal fp32; a subnormal amax (e < -126) lands on the upper clamp.
+// (se_of_amax in csrc/fp8_quant.h is the same rule returning the exponent, for the MX quantisers.)
 __device__ __forceinline__ void scale_of_amax(uint32_t bits, float& s, float& inv) {
   const int ef = (int)(bits >> 23);
   int se = 0;
@@ -46,19 +48,6 @@ __device__ __forceinline__ void scale_of_amax(uint32_t bits, float& s, float& in
   }
   s = __uint_as_float((uint32_t)(127 + se) << 23);
   inv = __uint_as_float((uint32_t)(127 - se) << 23);
-}
-
-// Two fp32 values -> two e4m3 bytes (low 16 bits), round to nearest even.  The hardware convert handles the
-// normal range (|v| >= 2^-6); the e4m3 subnormal range is rounded here as an integer count of 2^-9 steps
-// (0..8, where 8 is the encoding of 2^-6 itself), so the result does not depend on how the convert treats it.
-__device__ __forceinline__ uint32_t e4m3_sub(float v) {
-  return ((__float_as_uint(v) >> 24) & 0x80u) | (uint32_t)(int)rintf(fabsf(v) * 512.f);
-}
-__device__ __forceinline__ uint32_t e4m3_pk2(float v0, float v1) {
-  uint32_t p = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v0, v1, 0, false) & 0xffffu;
-  if (fabsf(v0) < 0.015625f) p = (p & 0xff00u) | e4m3_sub(v0);
-  if (fabsf(v1) < 0.015625f) p = (p & 0x00ffu) | (e4m3_sub(v1) << 8);
-  return p;
 }
 
 __device__ __forceinline__ void load8(const QuantTask& t, long v, float (&x)[8]) {
@@ -127,6 +116,61 @@ __global__ void __launch_bounds__(256) quant_tasks_kernel(QuantBatch b) {
     for (long i = nvec * 8 + tid; i < t.n; i += 256) t.q[i] = (uint8_t)(e4m3_pk2(load1(t, i) * s, 0.f) & 0xffu);
 }
 
+// ------------------------------------------------------------------------------------------------ MX quantiser
+// MXFP8 (OCP microscaling): e4m3 bytes plus one E8M0 scale byte per 32 consecutive elements of a row.  A row-major
+// [M, K] tensor with K % 32 == 0 is a flat run of n32 = M K / 32 blocks, block b = elements [32 b, 32 b + 32), its
+// scale byte at sc[b].  Per block the per-tensor rule above: se = se_of_amax(max|x|), q = RNE_e4m3(x 2^se), stored
+// scale 127 - se (the E8M0 code of the dequantisation scale 2^-se).  One pass, no state: a lane holds 8
+// consecutive elements, the four lanes of a block reduce amax with two xor-shuffles.
+struct MxQuantTask {
+  const void* src;
+  uint8_t* q;
+  uint8_t* sc;
+  long n32;  // blocks of 32 elements
+  int blk0, nblk;
+  int f32;   // source dtype: 0 bf16, 1 fp32
+  int pad;
+};
+struct MxQuantBatch {
+  int ntasks, nblocks;
+  MxQuantTask t[QT_MAX];
+};
+
+__global__ void __launch_bounds__(256) mx_quant_tasks_kernel(MxQuantBatch b) {
+  int ti = 0;
+  while (ti + 1 < b.ntasks && b.t[ti + 1].blk0 <= (int)blockIdx.x) ++ti;
+  const MxQuantTask& t = b.t[ti];
+  const int lb = blockIdx.x - t.blk0, tid = threadIdx.x;
+  DTC_ASSERT(lb >= 0 && lb < t.nblk);
+  const long nvec = t.n32 * 4;  // a multiple of 4: the four lanes of a block are all inside or all outside
+  for (long v = (long)lb * 256 + tid; v < nvec; v += (long)t.nblk * 256) {
+    float x[8];
+    if (t.f32) {
+      const f32x4 a = ((const f32x4*)t.src)[2 * v], c = ((const f32x4*)t.src)[2 * v + 1];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { x[i] = a[i]; x[4 + i] = c[i]; }
+    } else {
+      const u32x4 a = ((const u32x4*)t.src)[v];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        x[2 * i] = __uint_as_float(a[i] << 16);
+        x[2 * i + 1] = __uint_as_float(a[i] & 0xffff0000u);
+      }
+    }
+    uint32_t mx = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) mx = max(mx, __float_as_uint(x[i]) & 0x7fffffffu);
+    mx = amax_xor(amax_xor(mx, 1), 2);
+    const int se = se_of_amax(mx);
+    const float s = pow2_f(se);
+    u32x2 o;
+    o[0] = e4m3_pk4(x[0] * s, x[1] * s, x[2] * s, x[3] * s);
+    o[1] = e4m3_pk4(x[4] * s, x[5] * s, x[6] * s, x[7] * s);
+    ((u32x2*)t.q)[v] = o;
+    if ((v & 3) == 0) t.sc[v >> 2] = (uint8_t)(127 - se);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ GEMM
 // Mirror of ops/fp8.py Fp8GemmArgs (keep field order and types identical).
 struct Fp8GemmArgs {
@@ -154,8 +198,9 @@ struct Fp8GemmArgs {
 // single-instruction probe (benchmarks/mfma_f8_map_probe.hip: A one-hot in k, B small integers that identify k and
 // the column, 0 mismatches over 3 x 128 cases): lane l holds row / column l & 15, and byte j (0..31) of its eight
 // dwords is k = 32 (l >> 4) + j, for A and B alike.  So a lane's fragment is the 32 contiguous bytes at k-offset
-// 32 (l >> 4) of its row of a K-major operand.  The scale operands must be set in every lane (a lane's byte
-// scales its own 32-element block).
+// 32 (l >> 4) of its row of a K-major operand.  That pairing is all the per-tensor kernel needs (its scales are
+// equal); which k and which scale block the instruction assigns to a byte is stated at f8_frag below.  The scale
+// operands must be set in every lane.
 //
 // How the instruction sums (benchmarks/mfma_f8_sum_probe.hip, docs/NUMERICS.md): within a 32-element block the
 // products are aligned to the block's largest product exponent and cut toward zero 13 bits below it; different
@@ -186,16 +231,39 @@ __device__ __forceinline__ void f8_write(uint8_t* lds, int tid, const u32x4 (&r)
     *(u32x4*)(lds + row * 128 + ((slot ^ ((row >> 1) & 7)) << 4)) = r[i];
   }
 }
+// MXK = false: a lane's fragment is the 32 contiguous bytes (16-B slots 2 g, 2 g + 1) of its row.  With equal
+// scales any pairing of A bytes with the same B bytes gives the same products, which is all the map probe above
+// can see.  Unequal block scales show which k the instruction itself assigns to a byte (the scale-block cases of
+// benchmarks/mfma_f8_map_probe.hip, the mx family of benchmarks/mfma_f8_sum_probe.hip): dwords 0..3 of lane l
+// are k = 16 (l >> 4) + 0..15 and dwords 4..7 are k = 64 + 16 (l >> 4) + 0..15, and the scale of the 32-element
+// block b = k / 32 of row l & 15 is the byte supplied by lane 16 b + (l & 15).  MXK = true gathers in that order
+// (slots g and 4 + g), so that the instruction's k is the k of the K-major operand in memory and lane l supplies
+// the scale byte of block l >> 4 of its row.
+template <bool MXK>
 __device__ __forceinline__ i32x8 f8_frag(const uint8_t* lds, int row, int g) {
   const int sw = (row >> 1) & 7;
   const uint8_t* p = lds + row * 128;
-  const u32x4 lo = *(const u32x4*)(p + (((2 * g) ^ sw) << 4));
-  const u32x4 hi = *(const u32x4*)(p + (((2 * g + 1) ^ sw) << 4));
+  const u32x4 lo = *(const u32x4*)(p + (((MXK ? g : 2 * g) ^ sw) << 4));
+  const u32x4 hi = *(const u32x4*)(p + (((MXK ? 4 + g : 2 * g + 1) ^ sw) << 4));
   return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
 
-template <int TM, int EPI, bool OUTF32>
-__global__ void __launch_bounds__(256) gemm_fp8_kernel(Fp8GemmArgs a, int mt, int nwg) {
+// MX (block-scaled operands, ops/mxfp8.py): lane l feeds the instruction the E8M0 scale byte of block l >> 4 of
+// its fragment row for this k-step, byte kt * 4 + (l >> 4) of the row's scale row, fetched one k-step ahead like
+// the operands and replicated into the four bytes of the scale register (opsel i selects byte i, opsel 0 is used:
+// benchmarks/mfma_f8_map_probe.hip; the replication keeps the kernel independent of that); the epilogue's
+// 1/sa 1/sb multiply drops out.
+// FQ (MX, EPI_GELU, N % 32 == 0): the epilogue also emits the MX form of the bf16 gelu(u) it stores.
+struct MxGemmExtra {
+  const uint8_t* sa; long ldsa;  // E8M0 [M][K / 32]
+  const uint8_t* sb; long ldsb;  // E8M0 [N][K / 32]
+  uint8_t* gq;                   // FQ: e4m3 [M][N] of gelu(u)
+  uint8_t* gsc;                  // FQ: E8M0 [M][N / 32]
+};
+
+template <int TM, int EPI, bool OUTF32, bool MX = false, bool FQ = false>
+__global__ void __launch_bounds__(256) gemm_fp8_kernel(Fp8GemmArgs a, int mt, int nwg, MxGemmExtra x) {
+  static_assert(!FQ || (MX && EPI == EPI_GELU && !OUTF32), "the fused MX output belongs to the MX GELU-pair epilogue");
   constexpr int BM = 32 * TM;
   __shared__ __attribute__((aligned(16))) uint8_t lds[2][(BM + F8_BN) * 128];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
@@ -218,6 +286,22 @@ __global__ void __launch_bounds__(256) gemm_fp8_kernel(Fp8GemmArgs a, int mt, in
   __syncthreads();
 
   const int fr = lane & 15, fg = lane >> 4;
+  // MX: the scale bytes of this lane's fragment rows (rows past the edge clamp, as the operand loads do)
+  const uint8_t* psa[MX ? TM : 1];
+  const uint8_t* psb[MX ? 4 : 1];
+  int sca[MX ? TM : 1], scb[MX ? 4 : 1];
+  if constexpr (MX) {
+#pragma unroll
+    for (int m = 0; m < TM; ++m) {
+      psa[m] = x.sa + (long)min(mb + wr * 16 * TM + m * 16 + fr, M - 1) * x.ldsa + fg;
+      sca[m] = psa[m][0];
+    }
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      psb[n] = x.sb + (long)min(nb + wc * 64 + n * 16 + fr, N - 1) * x.ldsb + fg;
+      scb[n] = psb[n][0];
+    }
+  }
   for (int kt = 0; kt < nk; ++kt) {
     const uint8_t* cur = lds[kt & 1];
     const bool more = kt + 1 < nk;
@@ -225,17 +309,36 @@ __global__ void __launch_bounds__(256) gemm_fp8_kernel(Fp8GemmArgs a, int mt, in
       f8_load<BM>(a.A, a.lda, mb, M, (kt + 1) << 7, tid, ra);
       f8_load<F8_BN>(a.B, a.ldb, nb, N, (kt + 1) << 7, tid, rb);
     }
+    int nsa[MX ? TM : 1], nsb[MX ? 4 : 1];
+    if constexpr (MX) {
+      const int ko = more ? (kt + 1) * 4 : kt * 4;  // the last step re-reads its own bytes (in bounds)
+#pragma unroll
+      for (int m = 0; m < TM; ++m) nsa[m] = psa[m][ko];
+#pragma unroll
+      for (int n = 0; n < 4; ++n) nsb[n] = psb[n][ko];
+    }
     i32x8 fa[TM], fb[4];
 #pragma unroll
-    for (int m = 0; m < TM; ++m) fa[m] = f8_frag(cur, wr * 16 * TM + m * 16 + fr, fg);
+    for (int m = 0; m < TM; ++m) fa[m] = f8_frag<MX>(cur, wr * 16 * TM + m * 16 + fr, fg);
 #pragma unroll
-    for (int n = 0; n < 4; ++n) fb[n] = f8_frag(cur + BM * 128, wc * 64 + n * 16 + fr, fg);
+    for (int n = 0; n < 4; ++n) fb[n] = f8_frag<MX>(cur + BM * 128, wc * 64 + n * 16 + fr, fg);
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
-      for (int n = 0; n < 4; ++n)
-        acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[n], fa[m], acc[m][n], 0, 0, 0, 0x7f7f7f7f, 0,
-                                                                     0x7f7f7f7f);
+      for (int n = 0; n < 4; ++n) {
+        if constexpr (MX)
+          acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[n], fa[m], acc[m][n], 0, 0, 0,
+                                                                       scb[n] * 0x01010101, 0, sca[m] * 0x01010101);
+        else
+          acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[n], fa[m], acc[m][n], 0, 0, 0, 0x7f7f7f7f, 0,
+                                                                       0x7f7f7f7f);
+      }
+    if constexpr (MX) {
+#pragma unroll
+      for (int m = 0; m < TM; ++m) sca[m] = nsa[m];
+#pragma unroll
+      for (int n = 0; n < 4; ++n) scb[n] = nsb[n];
+    }
     if (more) {
       uint8_t* nxt = lds[(kt + 1) & 1];
       f8_write<BM>(nxt, tid, ra);
@@ -245,18 +348,27 @@ __global__ void __launch_bounds__(256) gemm_fp8_kernel(Fp8GemmArgs a, int mt, in
   }
 
   // epilogue: lane = row m (lane & 15), four consecutive columns n = 4 (lane >> 4) + 0..3 of each 16 x 16 fragment
-  const float isa = *a.inv_sa, isb = *a.inv_sb;
+  float isa = 1.f, isb = 1.f;
+  if constexpr (!MX) { isa = *a.inv_sa; isb = *a.inv_sb; }
 #pragma unroll
   for (int m = 0; m < TM; ++m) {
     const int row = mb + wr * 16 * TM + m * 16 + fr;
+    float gq[FQ ? 4 : 1][4];  // FQ: the bf16-rounded gelu(u) of this lane's four fragments (0 where not stored)
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const int col = nb + wc * 64 + n * 16 + fg * 4;
+      if constexpr (FQ) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gq[n][r] = 0.f;
+      }
       if (row >= M || col >= N) continue;  // N % 16 == 0: a fragment's columns are all in or all out
       DTC_ASSERT(col + 4 <= N);
       float o[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = acc[m][n][r] * isa * isb;  // powers of two: exact
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (MX) o[r] = acc[m][n][r];
+        else o[r] = acc[m][n][r] * isa * isb;  // powers of two: exact
+      }
       if (a.bias) {
         const f32x4 bb = *(const f32x4*)(a.bias + col);
 #pragma unroll
@@ -278,18 +390,46 @@ __global__ void __launch_bounds__(256) gemm_fp8_kernel(Fp8GemmArgs a, int mt, in
             gelu_tanh_and_grad_f(o[r], gv, dgv);
             o[r] = dgv;
             gb[r] = f2bf(gv);
+            if constexpr (FQ) gq[n][r] = (float)gb[r];
           }
           *(bf16x4*)((bf16*)a.aux_out + (long)row * a.ldc + col) = gb;
         }
         *(bf16x4*)((bf16*)a.C + (long)row * a.ldc + col) = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
       }
     }
+    if constexpr (FQ) {
+      // fragments 2 h and 2 h + 1 of the four lanes l & 15, l >> 4 = 0..3 are one 32-column block of row
+      // l & 15 (N % 32 == 0: a block is all in or all out); every lane takes part in the shuffles
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        uint32_t mx = 0u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          mx = max(mx, max(__float_as_uint(gq[2 * h][r]) & 0x7fffffffu, __float_as_uint(gq[2 * h + 1][r]) & 0x7fffffffu));
+        mx = amax_xor(amax_xor(mx, 16), 32);
+        const int se = se_of_amax(mx);
+        const float s = pow2_f(se);
+        const int col0 = nb + wc * 64 + h * 32;
+        if (row < M && col0 < N) {
+          DTC_ASSERT(col0 + 32 <= N);
+#pragma unroll
+          for (int f = 0; f < 2; ++f) {
+            const float* g4 = gq[2 * h + f];
+            *(uint32_t*)(x.gq + (long)row * N + col0 + f * 16 + fg * 4) =
+                e4m3_pk4(g4[0] * s, g4[1] * s, g4[2] * s, g4[3] * s);
+          }
+          if (fg == 0) x.gsc[(long)row * (N >> 5) + (col0 >> 5)] = (uint8_t)(127 - se);
+        }
+      }
+    }
   }
 }
+
 
 // Record of the last FP8 GEMM launch, written by the launch site (as note_launch in csrc/gemm.hip).
 struct LastLaunchFp8 {
   int bm, bn, tm, epi, c_f32, blocks;
+  int mx = 0;  // 0 per-tensor scales, 1 MX block scales, 2 MX with the fused MX output of gelu(u)
 };
 static LastLaunchFp8 g_last_fp8{};
 
@@ -308,7 +448,7 @@ static int launch_fp8(const Fp8GemmArgs& a, hipStream_t st) {
   constexpr int BM = 32 * TM;
   const int mt = (a.M + BM - 1) / BM, nt = (a.N + F8_BN - 1) / F8_BN;
   const int nwg = mt * nt;
-  hipLaunchKernelGGL((gemm_fp8_kernel<TM, EPI, OUTF32>), dim3(nwg), dim3(256), 0, st, a, mt, nwg);
+  hipLaunchKernelGGL((gemm_fp8_kernel<TM, EPI, OUTF32>), dim3(nwg), dim3(256), 0, st, a, mt, nwg, MxGemmExtra{});
   DTC_CHECK_LAUNCH();
   g_last_fp8 = LastLaunchFp8{BM, F8_BN, TM, EPI, OUTF32 ? 1 : 0, nwg};
   return 0;
@@ -319,6 +459,25 @@ static int launch_fp8_epi(const Fp8GemmArgs& a, hipStream_t st) {
   if (a.epi == EPI_STORE) return a.c_f32 ? launch_fp8<TM, EPI_STORE, true>(a, st) : launch_fp8<TM, EPI_STORE, false>(a, st);
   if (a.epi == EPI_RESID) return launch_fp8<TM, EPI_RESID, true>(a, st);
   return launch_fp8<TM, EPI_GELU, false>(a, st);
+}
+
+template <int TM, int EPI, bool OUTF32, bool FQ>
+static int launch_mxfp8(const Fp8GemmArgs& a, const MxGemmExtra& x, hipStream_t st) {
+  constexpr int BM = 32 * TM;
+  const int mt = (a.M + BM - 1) / BM, nt = (a.N + F8_BN - 1) / F8_BN;
+  const int nwg = mt * nt;
+  hipLaunchKernelGGL((gemm_fp8_kernel<TM, EPI, OUTF32, true, FQ>), dim3(nwg), dim3(256), 0, st, a, mt, nwg, x);
+  DTC_CHECK_LAUNCH();
+  g_last_fp8 = LastLaunchFp8{BM, F8_BN, TM, EPI, OUTF32 ? 1 : 0, nwg, FQ ? 2 : 1};
+  return 0;
+}
+
+template <int TM>
+static int launch_mxfp8_epi(const Fp8GemmArgs& a, const MxGemmExtra& x, hipStream_t st) {
+  if (a.epi == EPI_STORE)
+    return a.c_f32 ? launch_mxfp8<TM, EPI_STORE, true, false>(a, x, st) : launch_mxfp8<TM, EPI_STORE, false, false>(a, x, st);
+  if (a.epi == EPI_RESID) return launch_mxfp8<TM, EPI_RESID, true, false>(a, x, st);
+  return x.gq ? launch_mxfp8<TM, EPI_GELU, false, true>(a, x, st) : launch_mxfp8<TM, EPI_GELU, false, false>(a, x, st);
 }
 
 static int g_fp8_force_tm = 0;  // ops/fp8.py set_tile_m: 0 = by grid size, 64 / 128 = that tile height (A/B, tests)
@@ -373,8 +532,45 @@ int dtc_gemm_fp8(const Fp8GemmArgs* a, hipStream_t st) {
 
 int dtc_gemm_fp8_last_launch(int* out) {
   out[0] = g_last_fp8.bm; out[1] = g_last_fp8.bn; out[2] = g_last_fp8.tm; out[3] = g_last_fp8.epi;
-  out[4] = g_last_fp8.c_f32; out[5] = g_last_fp8.blocks; out[6] = 0; out[7] = 0;
+  out[4] = g_last_fp8.c_f32; out[5] = g_last_fp8.blocks; out[6] = g_last_fp8.mx; out[7] = 0;
   return 0;
+}
+
+int dtc_mxqt_task_bytes() { return (int)sizeof(MxQuantTask); }
+int dtc_mxqt_batch_bytes() { return (int)sizeof(MxQuantBatch); }
+
+// MX quantiser over a task table: one launch, no state.  Stream-ordered, capturable.
+int dtc_quant_mxfp8_tasks(const MxQuantBatch* b, hipStream_t st) {
+  DTC_HOST_CHECK(b->ntasks >= 1 && b->ntasks <= QT_MAX && b->nblocks >= b->ntasks);
+  for (int i = 0; i < b->ntasks; ++i) {
+    const MxQuantTask& t = b->t[i];
+    DTC_HOST_CHECK(t.n32 >= 1 && t.nblk >= 1 && t.src && t.q && t.sc);
+    DTC_HOST_CHECK(((uintptr_t)t.src & 15) == 0 && ((uintptr_t)t.q & 7) == 0);
+    DTC_HOST_CHECK(t.blk0 == (i ? b->t[i - 1].blk0 + b->t[i - 1].nblk : 0));
+  }
+  DTC_HOST_CHECK(b->t[b->ntasks - 1].blk0 + b->t[b->ntasks - 1].nblk == b->nblocks);
+  hipLaunchKernelGGL(mx_quant_tasks_kernel, dim3(b->nblocks), dim3(256), 0, st, *b);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+// The MX GEMM: a's inv_sa / inv_sb are unused; x carries the operands' scale bytes and, for EPI_GELU with
+// N % 32 == 0, optionally the MX output of gelu(u) (gq and gsc both set, or neither).
+int dtc_gemm_mxfp8(const Fp8GemmArgs* a, const MxGemmExtra* x, hipStream_t st) {
+  DTC_HOST_CHECK(a->M >= 1 && a->N >= 16 && a->K >= 128 && a->K % 128 == 0 && a->N % 16 == 0);
+  DTC_HOST_CHECK(a->lda >= a->K && a->ldb >= a->K && a->lda % 16 == 0 && a->ldb % 16 == 0 && a->ldc >= a->N);
+  DTC_HOST_CHECK(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0 && ((uintptr_t)a->C & 15) == 0);
+  DTC_HOST_CHECK(a->ldc % 4 == 0 && x->sa && x->sb && x->ldsa >= a->K / 32 && x->ldsb >= a->K / 32);
+  DTC_HOST_CHECK(a->epi == EPI_STORE || a->epi == EPI_RESID || a->epi == EPI_GELU);
+  DTC_HOST_CHECK(a->epi != EPI_RESID || (a->c_f32 && a->aux && a->ldaux >= a->N && a->ldaux % 4 == 0 &&
+                                         ((uintptr_t)a->aux & 15) == 0));
+  DTC_HOST_CHECK(a->epi != EPI_GELU || (!a->c_f32 && a->aux_out && ((uintptr_t)a->aux_out & 7) == 0));
+  DTC_HOST_CHECK(!a->bias || ((uintptr_t)a->bias & 15) == 0);
+  DTC_HOST_CHECK((x->gq != nullptr) == (x->gsc != nullptr));
+  DTC_HOST_CHECK(!x->gq || (a->epi == EPI_GELU && a->N % 32 == 0 && ((uintptr_t)x->gq & 3) == 0));
+  const long t128 = (long)((a->M + 127) / 128) * ((a->N + F8_BN - 1) / F8_BN);
+  const int tm = g_fp8_force_tm ? g_fp8_force_tm : (t128 >= fp8_cu_count() ? 4 : 2);
+  return tm == 4 ? launch_mxfp8_epi<4>(*a, *x, st) : launch_mxfp8_epi<2>(*a, *x, st);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 // float atomics -> bitwise reproducible).  Rows wider than a wave can hold (forward D > 2048, backward
 // D > 1024, up to 8192) are spread over the waves of a block: the ln_*_wide kernels below.
 #include "common.h"
+#include "fp8_quant.h"
 #include <cstdlib>
 
 namespace {
@@ -16,12 +17,16 @@ namespace {
 // resid (optional): the row is x + resid (the residual add of the producing layer, moved here from its
 // GEMM epilogue), written to x_out (may alias x) before it is normalised.
 // XB: x is bf16 (a bf16 GEMM output; the sum x + resid is fp32 in x_out, which must not alias x)
-template <int NV, int RPW, bool XB = false>
+// MX (bf16 y, D % 32 == 0; mq / msc are unused without it): the MXFP8 form of the bf16 y that is stored goes to mq / msc, the
+// same bytes as the stand-alone quantiser gives on y (csrc/gemm_fp8.hip mx_quant_tasks_kernel).  A lane holds
+// columns 4 (lane + 64 i) .. + 3, so a 32-column block is 8 consecutive lanes of one i (all inside or all outside
+// the row: D / 4 is a multiple of 8): three xor-shuffles, one 4-byte store per lane, one scale byte per 8 lanes.
+template <int NV, int RPW, bool XB = false, bool MX = false>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(const void* x, const float* __restrict__ resid, float* x_out,
                                                      const float* __restrict__ g,
                                                      const float* __restrict__ b, void* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     int M, int D, float eps, int out_f32) {
+                                                     int M, int D, float eps, int out_f32, uint8_t* mq, uint8_t* msc) {
   const int lane = threadIdx.x & 63;
   const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
   if (row0 >= M) return;
@@ -98,8 +103,21 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const void* x, const float*
       int c = lane + 64 * i;
       if (c < D4) {
         f32x4 o = (v[q][i] - mean) * rstd * gv[i] + bv[i];
-        if (out_f32) ((f32x4*)((float*)y + (long)row * D))[c] = o;
-        else ((bf16x4*)((bf16*)y + (long)row * D))[c] = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
+        if constexpr (MX) {
+          const bf16x4 ob = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
+          ((bf16x4*)((bf16*)y + (long)row * D))[c] = ob;
+          const float r0 = (float)ob[0], r1 = (float)ob[1], r2 = (float)ob[2], r3 = (float)ob[3];
+          uint32_t mx = max(max(__float_as_uint(r0) & 0x7fffffffu, __float_as_uint(r1) & 0x7fffffffu),
+                            max(__float_as_uint(r2) & 0x7fffffffu, __float_as_uint(r3) & 0x7fffffffu));
+          mx = amax_xor(amax_xor(amax_xor(mx, 1), 2), 4);
+          const int se = se_of_amax(mx);
+          const float s = pow2_f(se);
+          ((uint32_t*)(mq + (long)row * D))[c] = e4m3_pk4(r0 * s, r1 * s, r2 * s, r3 * s);
+          if ((lane & 7) == 0) msc[(long)row * (D >> 5) + (c >> 3)] = (uint8_t)(127 - se);
+        } else {
+          if (out_f32) ((f32x4*)((float*)y + (long)row * D))[c] = o;
+          else ((bf16x4*)((bf16*)y + (long)row * D))[c] = bf16x4{f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
+        }
       }
     }
   }
@@ -639,7 +657,7 @@ int dtc_add_layernorm_fwd(const float* x, const float* resid, float* x_out, cons
   // one row per wave (two rows per wave measured neutral on GPT-2 small, round 3: removed)
   dim3 grid((M + 3) / 4);
   DTC_NV_SWITCH(nv, hipLaunchKernelGGL((ln_fwd_kernel<NVC, 1>), grid, dim3(256), 0, st, x, resid, x_out, g, b, y, mean,
-                                       rstd, M, D, eps, out_f32));
+                                       rstd, M, D, eps, out_f32, (uint8_t*)nullptr, (uint8_t*)nullptr));
   DTC_CHECK_LAUNCH();
   return 0;
 }
@@ -653,7 +671,7 @@ int dtc_add_layernorm_fwd_bf16(const bf16* d, const float* resid, float* x_out, 
   int nv = (D / 4 + 63) / 64;
   dim3 grid((M + 3) / 4);
   DTC_NV_SWITCH(nv, hipLaunchKernelGGL((ln_fwd_kernel<NVC, 1, true>), grid, dim3(256), 0, st, d, resid, x_out, g, b, y,
-                                       mean, rstd, M, D, eps, out_f32));
+                                       mean, rstd, M, D, eps, out_f32, (uint8_t*)nullptr, (uint8_t*)nullptr));
   DTC_CHECK_LAUNCH();
   return 0;
 }
@@ -661,6 +679,29 @@ int dtc_add_layernorm_fwd_bf16(const bf16* d, const float* resid, float* x_out, 
 int dtc_layernorm_fwd(const float* x, const float* g, const float* b, void* y, float* mean, float* rstd, int M, int D,
                       float eps, int out_f32, hipStream_t st) {
   return dtc_add_layernorm_fwd(x, nullptr, nullptr, g, b, y, mean, rstd, M, D, eps, out_f32, st);
+}
+
+// The narrow forward with the MXFP8 form of its bf16 y as a further output (mq e4m3 [M][D], msc E8M0 [M][D / 32]).
+// x_bf16 = 0: x fp32, resid / x_out optional (x_out may alias x); 1: x bf16, resid and x_out required (the bf16
+// branch of the add-LayerNorm).  D % 32 == 0 and D <= 2048: wider rows have no fused form (error 2003).
+int dtc_layernorm_fwd_mx(const void* x, int x_bf16, const float* resid, float* x_out, const float* g, const float* b,
+                         void* y, float* mean, float* rstd, int M, int D, float eps, uint8_t* mq, uint8_t* msc,
+                         hipStream_t st) {
+  if (const int e = ln_width_error(D)) return e;
+  if (D > LN_FWD_NARROW_D || D % 32) return 2003;
+  DTC_HOST_CHECK(M >= 1 && x && y && mq && msc && ((uintptr_t)mq & 3) == 0);
+  DTC_HOST_CHECK(!x_bf16 || (resid && x_out && (const void*)x != (const void*)x_out));
+  int nv = (D / 4 + 63) / 64;
+  dim3 grid((M + 3) / 4);
+  if (x_bf16) {
+    DTC_NV_SWITCH(nv, hipLaunchKernelGGL((ln_fwd_kernel<NVC, 1, true, true>), grid, dim3(256), 0, st, x, resid, x_out, g,
+                                         b, y, mean, rstd, M, D, eps, 0, mq, msc));
+  } else {
+    DTC_NV_SWITCH(nv, hipLaunchKernelGGL((ln_fwd_kernel<NVC, 1, false, true>), grid, dim3(256), 0, st, x, resid, x_out,
+                                         g, b, y, mean, rstd, M, D, eps, 0, mq, msc));
+  }
+  DTC_CHECK_LAUNCH();
+  return 0;
 }
 
 // DTC_LN_BWD_ITER: row groups of LN_BWD_ROWS per block.  2 (512 blocks at 8192 rows): half the partial

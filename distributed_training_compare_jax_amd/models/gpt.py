@@ -31,6 +31,7 @@ from ..ops import embedding as E
 from ..ops import gemm as G
 from ..ops import layernorm as LN
 from ..ops import fp8 as F8
+from ..ops import mxfp8 as MX
 from ..ops import ln_fused as LF
 from ..ops import xent as X
 from ..ops.reduce import GradReducer
@@ -174,6 +175,8 @@ class GPTStage:
         self._sp_idx: Dict = {}
         # FP8 forward (enable_fp8_forward): qkv / out_proj / fc1 / fc2 forwards on e4m3 operands
         self.fp8 = False
+        # MXFP8 forward (enable_mxfp8_forward): the same four GEMMs on block-scaled e4m3 operands
+        self.mx = False
 
     def enable_fp8_forward(self):
         """Run the four layer GEMMs of every block forward on the FP8 kernel (``ops/fp8.py``): each input (the
@@ -184,6 +187,15 @@ class GPTStage:
         assert self.tp.size == 1 and not self._fuse_fwd and not self.sp
         self.flat.enable_fp8([f"h.{l}.{n}.w" for l in self.layout.layers for n in ("qkv", "out", "fc1", "fc2")])
         self.fp8 = True
+
+    def enable_mxfp8_forward(self):
+        """As :meth:`enable_fp8_forward` with MXFP8 operands (``ops/mxfp8.py``: e4m3 bytes and one power-of-two
+        scale per 32 elements of k) and the MXFP8 weight mirror (``FlatParams.enable_mxfp8``).  The LayerNorms and
+        the fc1 GELU epilogue write the MX form of their bf16 output themselves (``DTC_MX_FUSE``, d_model <= 2048);
+        the attention output goes through the one-pass stand-alone quantiser.  The backward is unchanged."""
+        assert self.tp.size == 1 and not self._fuse_fwd and not self.sp and not self.fp8
+        self.flat.enable_mxfp8([f"h.{l}.{n}.w" for l in self.layout.layers for n in ("qkv", "out", "fc1", "fc2")])
+        self.mx = True
 
     def set_wgrad_group(self, layers: int):
         """Defer weight gradients to grouped launches of ``layers`` consecutive layers (0 = all layers of
@@ -354,9 +366,51 @@ class GPTStage:
         """dtype of the out_proj / fc2 outputs the LayerNorm pass adds to the residual (DTC_FWD_BF16)."""
         return torch.bfloat16 if _FWD_BF16 and self.act_dtype == torch.bfloat16 else torch.float32
 
+    def _block_forward_mx(self, l: int, x: torch.Tensor, batch: int, ctx: Dict) -> torch.Tensor:
+        """:meth:`block_forward` with the four layer GEMMs on MXFP8 operands (enable_mxfp8_forward; tp == 1, no
+        LayerNorm-GEMM fusion).  Every LayerNorm that feeds a layer GEMM returns the MX form of its output with it,
+        and hands it on to the next layer beside ``ctx[("ln1", l + 1)]``; ``lnf`` feeds the bf16 lm_head and has
+        none.  ``ctx[l]`` holds the same tensors as the bf16 forward's."""
+        self._await_params(l)
+        f, p = self.flat, f"h.{l}."
+        T = x.shape[0] // batch
+        act = self.act_dtype
+        pre = ctx.pop(("ln1", l), None)  # LN1 (and its MX form) already produced by the previous layer
+        y1q = ctx.pop(("ln1_mx", l), None)
+        if pre is None:
+            pre, y1q = MX.layernorm_fwd_mx(x, f.p(p + "ln1.g"), f.p(p + "ln1.b"), self.eps, act)
+        y1, mu1, rs1 = pre
+        if y1q is None:
+            y1q = MX.quant_mxfp8(y1)
+        qkv = MX.linear_mxfp8(y1q, f.wmx(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=act)
+        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local)
+        o = o.view(batch * T, -1)
+        oq = MX.quant_mxfp8(o)
+        if _ADD_LN:  # residual add in the LayerNorm pass, as block_forward
+            br = MX.linear_mxfp8(oq, f.wmx(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype)
+            x2, (y2, mu2, rs2), y2q = MX.add_layernorm_fwd_mx(br, x, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, act)
+        else:
+            x2 = MX.linear_resid_mxfp8(oq, f.wmx(p + "out.w"), f.p(p + "out.b"), x)
+            (y2, mu2, rs2), y2q = MX.layernorm_fwd_mx(x2, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, act)
+        u, gact, gq = MX.linear_gelu_mxfp8(y2q, f.wmx(p + "fc1.w"), f.p(p + "fc1.b"), out_dtype=act, quant_out=True)
+        nxt = f"h.{l + 1}.ln1" if (l + 1) in self.layout.layers else ("lnf" if self.layout.has_head else None)
+        if _ADD_LN and nxt is not None:
+            br = MX.linear_mxfp8(gq, f.wmx(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype)
+            if nxt == "lnf":
+                x3, ctx["lnf_pre"] = LN.add_layernorm_fwd(br, x2, f.p("lnf.g"), f.p("lnf.b"), self.eps, act)
+            else:
+                x3, ctx[("ln1", l + 1)], ctx[("ln1_mx", l + 1)] = MX.add_layernorm_fwd_mx(
+                    br, x2, f.p(nxt + ".g"), f.p(nxt + ".b"), self.eps, act)
+        else:
+            x3 = MX.linear_resid_mxfp8(gq, f.wmx(p + "fc2.w"), f.p(p + "fc2.b"), x2)
+        ctx[l] = (x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch)
+        return x3
+
     def block_forward(self, l: int, x: torch.Tensor, batch: int, ctx: Dict) -> torch.Tensor:
         if self.sp:
             return self._block_forward_sp(l, x, batch, ctx)
+        if self.mx:
+            return self._block_forward_mx(l, x, batch, ctx)
         self._await_params(l)
         f, p = self.flat, f"h.{l}."
         tp = self.tp

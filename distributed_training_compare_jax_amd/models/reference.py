@@ -27,8 +27,9 @@ class _FakeQuantLinear(torch.autograd.Function):
     matmul's on the unquantised operands (straight-through)."""
 
     @staticmethod
-    def forward(ctx, x, w, bf16_inputs, sink):
+    def forward(ctx, x, w, bf16_inputs, sink, mx=False):
         from ..ops import fp8 as F8
+        from ..ops import mxfp8 as MX
 
         ctx.save_for_backward(x, w)
         x2 = x.reshape(-1, x.shape[-1])
@@ -36,15 +37,19 @@ class _FakeQuantLinear(torch.autograd.Function):
             x2 = x2.to(torch.bfloat16).float()
         if sink is not None:
             sink.append(x2.detach().clone())
-        xq = F8.dequant(F8.quant_e4m3(x2.contiguous()))
-        wq = F8.dequant(F8.quant_e4m3(w.detach().to(torch.bfloat16).contiguous()))
+        if mx:  # block scales along k (ops/mxfp8.py) for both operands
+            xq = MX.dequant(MX.quant_mxfp8(x2.contiguous()))
+            wq = MX.dequant(MX.quant_mxfp8(w.detach().to(torch.bfloat16).contiguous()))
+        else:
+            xq = F8.dequant(F8.quant_e4m3(x2.contiguous()))
+            wq = F8.dequant(F8.quant_e4m3(w.detach().to(torch.bfloat16).contiguous()))
         return (xq @ wq.t()).view(*x.shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         g2 = g.reshape(-1, g.shape[-1])
-        return g @ w, g2.t() @ x.reshape(-1, x.shape[-1]), None, None
+        return g @ w, g2.t() @ x.reshape(-1, x.shape[-1]), None, None, None
 
 
 def oracle_loss(cfg: ModelConfig, params: dict, ids: torch.Tensor, labels: torch.Tensor, seed: int, step: int,
@@ -55,9 +60,14 @@ def oracle_loss(cfg: ModelConfig, params: dict, ids: torch.Tensor, labels: torch
     ``fake_quant`` (default off): the four layer GEMMs of every block (qkv, out_proj, fc1, fc2) run as
     :class:`_FakeQuantLinear`, the statement of ``TrainConfig.fwd_gemm_dtype: fp8``; the lm_head stays as it is.
     ``quant_bf16_inputs`` rounds each quantiser's activation input to bf16 first (what the bf16 engine feeds it);
-    ``quant_inputs``: a list that collects every quantiser's activation input, in call order."""
+    ``quant_inputs``: a list that collects every quantiser's activation input, in call order.
+    ``fake_quant="mx"``: the same with the MXFP8 quantiser of ``ops/mxfp8.py`` (one scale per 32 elements of k), the
+    statement of ``fwd_gemm_dtype: mxfp8``."""
+    if fake_quant not in (False, True, "mx"):
+        raise ValueError(f"fake_quant={fake_quant!r}: expected False, True or 'mx'")
     if fake_quant:
-        mm = lambda a, w: _FakeQuantLinear.apply(a, w, quant_bf16_inputs, quant_inputs)  # noqa: E731
+        mx = fake_quant == "mx"
+        mm = lambda a, w: _FakeQuantLinear.apply(a, w, quant_bf16_inputs, quant_inputs, mx)  # noqa: E731
     else:
         mm = lambda a, w: a @ w.t()  # noqa: E731
     B, T = ids.shape

@@ -200,6 +200,12 @@ def _declare(lib):
         "dtc_gemm_fp8": ([vp, vp], i),
         "dtc_gemm_fp8_set_tile_m": ([i], i),
         "dtc_gemm_fp8_last_launch": ([ctypes.POINTER(c_int)], i),
+        # MXFP8 forward path (csrc/gemm_fp8.hip, csrc/norm_reduce.hip); the argument structs live in ops/mxfp8.py
+        "dtc_quant_mxfp8_tasks": ([vp, vp], i),
+        "dtc_mxqt_task_bytes": ([], i),
+        "dtc_mxqt_batch_bytes": ([], i),
+        "dtc_gemm_mxfp8": ([vp, vp, vp], i),
+        "dtc_layernorm_fwd_mx": ([vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, f, vp, vp, vp], i),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)

@@ -178,7 +178,10 @@ def last_launch_fp8() -> LastLaunchFp8:
     out = (ctypes.c_int * 8)()
     N.check(N.lib().dtc_gemm_fp8_last_launch(out), "dtc_gemm_fp8_last_launch")
     v = list(out)
-    return LastLaunchFp8((v[0], v[1]), VARIANTS.get(v[2], "none"), EPI_NAMES.get(v[3], "none"), bool(v[4]), v[5])
+    variant = VARIANTS.get(v[2], "none")
+    if v[6]:  # the launch was an MX kernel of the same tile (ops/mxfp8.py last_launch_mxfp8 says more)
+        variant = "mx" + variant
+    return LastLaunchFp8((v[0], v[1]), variant, EPI_NAMES.get(v[3], "none"), bool(v[4]), v[5])
 
 
 def set_tile_m(bm: int = 0):

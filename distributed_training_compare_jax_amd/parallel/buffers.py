@@ -78,6 +78,8 @@ class FlatParams:
         self._mirror_t_buf = None
         # FP8 weight mirror (enable_fp8): name -> (slot, ops.fp8.Fp8Tensor), rebuilt wherever the bf16 mirror is
         self.mirror_fp8: Dict[str, Tuple[Slot, object]] = {}
+        # MXFP8 weight mirror (enable_mxfp8): name -> (slot, ops.mxfp8.MxFp8Tensor), rebuilt at the same sites
+        self.mirror_mx: Dict[str, Tuple[Slot, object]] = {}
 
     # -- init -----------------------------------------------------------------
     def init_canonical(self, seed: int):
@@ -94,6 +96,7 @@ class FlatParams:
             cast_to_bf16(self.params[: self.n_mirror], self.mirror[: self.n_mirror])
             self.refresh_transposed()
         self.refresh_fp8()
+        self.refresh_mxfp8()
 
     # -- transposed mirror --------------------------------------------------------
     def enable_transposed(self, names: List[str]):
@@ -164,6 +167,52 @@ class FlatParams:
         ent = list(self.mirror_fp8.items())[i0:i1]
         src = [self.w(n) if self.use_mirror else self.p(n).to(torch.bfloat16) for n, _ in ent]
         F8.quant_e4m3_batch(src, [t.q for _, (_, t) in ent], self._fp8_state[i0:i1])
+
+    # -- MXFP8 weight mirror -----------------------------------------------------------
+    def enable_mxfp8(self, names: List[str]):
+        """Keep an MXFP8 copy (e4m3 bytes + one E8M0 scale byte per 32 elements of a row, ``ops/mxfp8.py``) of these
+        2-D mirrored weights: ``quant_mxfp8`` of the bf16 mirror (of the master rounded to bf16 where no mirror is
+        kept).  Rebuilt by :meth:`refresh_mxfp8` wherever the bf16 mirror is rebuilt or written; not part of a
+        checkpoint."""
+        from ..ops import mxfp8 as MX
+
+        names = [n for n in names if n in self.slots and self.slots[n].spec.mirror and len(self.slots[n].shape) == 2]
+        if not names:
+            return
+        names.sort(key=lambda n: self.slots[n].offset)
+        total = sum(self.slots[n].numel for n in names)
+        self._mx_buf = torch.zeros(total, dtype=torch.uint8, device=self.device)
+        self._mx_sc = torch.zeros(total // MX.BLOCK, dtype=torch.uint8, device=self.device)
+        off = 0
+        for n in names:
+            sl = self.slots[n]
+            rows, cols = sl.shape
+            assert cols % MX.BLOCK == 0 and off % MX.BLOCK == 0, (n, sl.shape)
+            q = self._mx_buf[off:off + sl.numel].view(rows, cols)
+            sc = self._mx_sc[off // MX.BLOCK:(off + sl.numel) // MX.BLOCK].view(rows, cols // MX.BLOCK)
+            self.mirror_mx[n] = (sl, MX.MxFp8Tensor(q, sc))
+            off += sl.numel
+        self.refresh_mxfp8()
+
+    def refresh_mxfp8(self, lo: int = 0, hi: int = None):
+        """Requantise the MXFP8 copies of the weights inside flat[lo:hi] (one batched quantiser call)."""
+        if not self.mirror_mx:
+            return
+        from ..ops import mxfp8 as MX
+
+        hi = self.numel if hi is None else hi
+        ent = [(n, t) for n, (sl, t) in self.mirror_mx.items() if sl.offset >= lo and sl.offset + sl.numel <= hi]
+        if not ent:
+            return
+        src = [self.w(n) if self.use_mirror else self.p(n).to(torch.bfloat16) for n, _ in ent]
+        MX.quant_mxfp8_batch(src, [t for _, t in ent])
+
+    def wmx(self, name: str):
+        """The MXFP8 copy of a weight (``ops.mxfp8.MxFp8Tensor``); raises when none is kept."""
+        e = self.mirror_mx.get(name)
+        if e is None:
+            raise KeyError(f"no MXFP8 mirror of {name!r} (FlatParams.enable_mxfp8)")
+        return e[1]
 
     def w8(self, name: str):
         """The e4m3 copy of a weight (``ops.fp8.Fp8Tensor``); raises when none is kept."""

@@ -65,9 +65,9 @@ class Engine:
                 model_cfg = replace(model_cfg, vocab_pad_multiple=mult)
                 self.mcfg = model_cfg
         # FP8 forward GEMMs (models/gpt.py enable_fp8_forward): what it does not cover is refused here, by name
-        if train_cfg.fwd_gemm_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"fwd_gemm_dtype={train_cfg.fwd_gemm_dtype!r}: expected 'bf16' or 'fp8'")
-        if train_cfg.fwd_gemm_dtype == "fp8":
+        if train_cfg.fwd_gemm_dtype not in ("bf16", "fp8", "mxfp8"):
+            raise ValueError(f"fwd_gemm_dtype={train_cfg.fwd_gemm_dtype!r}: expected 'bf16', 'fp8' or 'mxfp8'")
+        if train_cfg.fwd_gemm_dtype in ("fp8", "mxfp8"):
             why = None
             if train_cfg.dtype == "fp32":
                 why = "dtype=fp32 (the exact-fp32 parity mode has no reduced-precision GEMMs)"
@@ -81,7 +81,7 @@ class Engine:
                 why = (f"d_model={model_cfg.d_model}, d_ff={model_cfg.d_ff} (the FP8 GEMM's k-step is 128: both must "
                        "be multiples of 128)")
             if why:
-                raise ValueError(f"fwd_gemm_dtype=fp8 cannot be combined with {why}")
+                raise ValueError(f"fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} cannot be combined with {why}")
         rehearse = bool(train_cfg.dp_comm_rehearsal and dp == 1 and dist.is_available() and dist.is_initialized())
         self.mesh: Mesh = build_mesh(dinfo.rank, dinfo.world, dp, tp, pp, dp_group_always=rehearse)
         m = self.mesh
@@ -353,6 +353,8 @@ class Engine:
                                         bwd=bool(lnf & 2) and has_wt)
         if train_cfg.fwd_gemm_dtype == "fp8":
             self.stage.enable_fp8_forward()
+        elif train_cfg.fwd_gemm_dtype == "mxfp8":
+            self.stage.enable_mxfp8_forward()
         if on_gpu:
             self._reserve_workspaces()
 

@@ -208,6 +208,7 @@ class FusedAdamW:
                 O.adamw_tr(f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.mirror, f.n_mirror, plan, self.step_t,
                            self.sumsq, c.lr, c.b1, c.b2, c.eps, c.weight_decay, c.grad_clip)
                 f.refresh_fp8(lo, hi)
+                f.refresh_mxfp8(lo, hi)
                 return
         O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[lo:hi], f.exp_avg_sq[lo:hi],
                      f.mirror[lo:lo + max(nm, 4)] if nm > 0 else None, nm, self.step_t, self.sumsq, c.lr, c.b1, c.b2,
@@ -215,6 +216,7 @@ class FusedAdamW:
         if nm > 0:
             f.refresh_transposed(lo, hi)
         f.refresh_fp8(lo, hi)
+        f.refresh_mxfp8(lo, hi)
 
     def step(self):
         self.norm()
