@@ -38,7 +38,10 @@ are optional and default to the reference behaviour:
   ``pp_head_cost`` blocks on the last stage -- default from FLOPs, ``parallel/mesh.py``; ``even``: the
   remainder layers to the earliest stages), ``dp_grad_dtype`` / ``pp_comm_dtype`` / ``tp_comm_dtype`` (``bf16``: the DP
   gradient buckets / PP stage messages / TP partial sums travel as bf16 and are summed in fp32,
-  ``ops/payload.py``, ``parallel/tp.py reduce_to``; the TP residual is added after the sum, unrounded).
+  ``ops/payload.py``, ``parallel/tp.py reduce_to``; the TP residual is added after the sum, unrounded),
+  ``pp_comm`` (``rccl`` | ``p2p``: the PP stage messages, loss sum and ``pp_clip: global`` norm as eager
+  process-group calls between graph segments, or as in-graph peer-to-peer kernels, ``parallel/p2p.py P2PPipe``:
+  one hipGraph per stage step at dp = 1; GPU, pp <= 8, tp = 1; default ``rccl``).
 """
 
 from __future__ import annotations
@@ -147,6 +150,12 @@ class TrainConfig:
     # fp32 | bf16 | auto: PP activation / gradient messages; auto = bf16 when the compute dtype is bf16 (5000-step
     # pp2 curve: the same gap to dp1 as fp32 messages; half the bytes of the latency-bound pp8 hops)
     pp_comm_dtype: str = "auto"
+    # rccl | p2p: how the PP stage messages, the PP loss sum and the pp_clip: global norm travel.  rccl = eager
+    # send/recv and all-reduces between graph segments (a cut per message exchange); p2p = stream-ordered kernels
+    # over IPC-mapped peer buffers (parallel/p2p.py P2PPipe), so a stage's step at dp == 1 is ONE hipGraph with no
+    # eager collective.  GPU only, 2 <= pp <= 8, tp == 1.  No auto: the default stays rccl until p2p has run across
+    # real GPUs (docs/CAPTURE.md)
+    pp_comm: str = "rccl"
     # fp32 | bf16 | auto: TP row-parallel / input-gradient partials (fp32 sums either way); auto = bf16 when the
     # compute dtype is bf16 (5000-step tp2 curve: the same gap to dp1 as fp32, profiles/r5_cross_strategy.md)
     tp_comm_dtype: str = "auto"

@@ -246,6 +246,70 @@ __global__ void p2p_ag_kernel(PeerTable t, int world, long n16_loc, long half_by
     out[i] = ((const u32x4*)(t.base[(int)(i / n16_loc)] + off))[i];
 }
 
+// ---------------------------------------------------------------- pipeline stage messages (pp_comm: p2p)
+// A point-to-point message between neighbouring pipeline stages, built from the signalling pattern of
+// the barrier above and PULLED by its receiver:
+//
+//   sender    payload -> a slot of its OWN buffer (pp_stage_kernel, or the producer wrote it there)
+//             kernel boundary
+//             pp_signal_kernel: __threadfence_system, release store of the step epoch into flag word
+//             `flag_idx` of the RECEIVER's buffer (system scope).  A send never waits.
+//   receiver  pp_wait_kernel: spins on its own flag word (system-scope acquire) until it is >= the step
+//             epoch; bounded like the barrier (error word 3000 + flag_idx, then proceeds)
+//             kernel boundary
+//             pp_pull_kernel: loads the sender's slot over the mapped pointer into the destination
+//             (16-byte pieces, any element type; optionally also the fp32 image of a bf16 message)
+//
+// No payload is ever stored remotely.  The step epoch is a device counter bumped once per step
+// (dtc_epoch_inc), so eager steps and graph replays advance it alike; each (direction, kind, microbatch)
+// has its own slot and flag word (parallel/p2p.py P2PPipe), written once per step.
+__global__ void pp_stage_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ slot, long n16, long slot_off,
+                                long buf_bytes) {
+  DTC_ASSERT(slot_off >= 0 && slot_off % 16 == 0 && slot_off + 16 * n16 <= buf_bytes);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) slot[i] = x[i];
+}
+
+__global__ void pp_signal_kernel(uint32_t* __restrict__ peer_flags, int flag_idx, const uint32_t* __restrict__ epoch) {
+  DTC_ASSERT(flag_idx >= 0 && flag_idx < FLAG_BYTES / 4);
+  if (threadIdx.x == 0) {
+    __threadfence_system();  // the slot's content (earlier kernels of this stream) before the signal
+    __hip_atomic_store(peer_flags + flag_idx, epoch[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+__global__ void pp_wait_kernel(const uint32_t* __restrict__ flags, int flag_idx, const uint32_t* __restrict__ epoch,
+                               int* __restrict__ err) {
+  DTC_ASSERT(flag_idx >= 0 && flag_idx < FLAG_BYTES / 4);
+  if (threadIdx.x == 0) {
+    const uint32_t e = epoch[0];
+    const uint64_t t0 = wall_clock();
+    while (__hip_atomic_load(flags + flag_idx, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < e) {
+      __builtin_amdgcn_s_sleep(2);
+      if (wall_clock() - t0 > 1000000000ull) {  // ~10 s at 100 MHz
+        atomicExch(err, 3000 + flag_idx);
+        break;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// out[i] = slot[i] (16-byte pieces); F32: the piece holds 8 bf16 values, whose exact fp32 images
+// (bits << 16) also go to out_f32[8 i .. 8 i + 7]
+template <bool F32>
+__global__ void pp_pull_kernel(const u32x4* __restrict__ slot, u32x4* __restrict__ out, u32x4* __restrict__ out_f32,
+                               long n16, long slot_off, long buf_bytes) {
+  DTC_ASSERT(slot_off >= 0 && slot_off % 16 == 0 && slot_off + 16 * n16 <= buf_bytes);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) {
+    const u32x4 v = slot[i];
+    out[i] = v;
+    if constexpr (F32) {
+      out_f32[2 * i] = u32x4{v[0] << 16, v[0] & 0xffff0000u, v[1] << 16, v[1] & 0xffff0000u};
+      out_f32[2 * i + 1] = u32x4{v[2] << 16, v[2] & 0xffff0000u, v[3] << 16, v[3] & 0xffff0000u};
+    }
+  }
+}
+
 // ---------------------------------------------------------------- intra-device stream flags
 // Cross-stream dependencies between two separately captured hipGraphs (main / side) on the SAME
 // device: a producer stream bumps flags[k] to its replay epoch (agent-scope release, after all of
@@ -486,6 +550,54 @@ int dtc_p2p_all_gather(const void* x, void* out, long loc_bytes, void* const* ba
   DTC_CHECK_LAUNCH();
   const int blocks = (int)std::min(1024L, std::max(1L, (n16 * world + 255) / 256));
   hipLaunchKernelGGL(p2p_ag_kernel, dim3(blocks), dim3(256), 0, st, t, world, n16, half_bytes, (u32x4*)out, epoch);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- pipeline stage messages (kernels above; slot table and flag indices: parallel/p2p.py P2PPipe)
+inline bool pp_args_ok(long n, long slot_off, long buf_bytes, int flag_idx) {
+  return n > 0 && n % 16 == 0 && slot_off >= 0 && slot_off % 16 == 0 && slot_off <= buf_bytes &&
+         n <= buf_bytes - slot_off && flag_idx >= 0 && flag_idx < FLAG_BYTES / 4;
+}
+
+// Send n bytes (a multiple of 16): copy x into this rank's slot at payload offset slot_off of its own buffer
+// (own_base; buf_bytes of payload behind the flag area), then store the step epoch into flag word flag_idx
+// of the receiver's buffer (peer_base).  x == nullptr: the producer already wrote the slot.  Never waits.
+int dtc_pp_send(const void* x, long n, void* own_base, long slot_off, long buf_bytes, void* peer_base, int flag_idx,
+                const uint32_t* epoch, hipStream_t st) {
+  if (!own_base || !peer_base || !epoch || !pp_args_ok(n, slot_off, buf_bytes, flag_idx) || ((uintptr_t)x & 15))
+    return 4001;
+  if (x) {
+    const long n16 = n / 16;
+    const int blocks = (int)std::min(1024L, std::max(1L, (n16 + 255) / 256));
+    hipLaunchKernelGGL(pp_stage_kernel, dim3(blocks), dim3(256), 0, st, (const u32x4*)x,
+                       (u32x4*)((unsigned char*)own_base + FLAG_BYTES + slot_off), n16, slot_off, buf_bytes);
+    DTC_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(pp_signal_kernel, dim3(1), dim3(64), 0, st, (uint32_t*)peer_base, flag_idx, epoch);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+// Receive n bytes: wait until this rank's flag word flag_idx (own_base) reaches the step epoch, then copy the
+// sender's slot (peer_base, payload offset slot_off, buf_bytes of payload in the SENDER's buffer) into out.
+// out_f32 (optional): the message is bf16 and its fp32 image (2 n bytes) is written in the same pass.
+int dtc_pp_recv(void* out, void* out_f32, long n, const void* peer_base, long slot_off, long buf_bytes,
+                const void* own_base, int flag_idx, const uint32_t* epoch, int* err, hipStream_t st) {
+  if (!out || !own_base || !peer_base || !epoch || !err || !pp_args_ok(n, slot_off, buf_bytes, flag_idx) ||
+      ((uintptr_t)out & 15) || ((uintptr_t)out_f32 & 15))
+    return 4001;
+  hipLaunchKernelGGL(pp_wait_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)own_base, flag_idx, epoch, err);
+  DTC_CHECK_LAUNCH();
+  const long n16 = n / 16;
+  const int blocks = (int)std::min(1024L, std::max(1L, (n16 + 255) / 256));
+  const u32x4* slot = (const u32x4*)((const unsigned char*)peer_base + FLAG_BYTES + slot_off);
+  if (out_f32)
+    hipLaunchKernelGGL(pp_pull_kernel<true>, dim3(blocks), dim3(256), 0, st, slot, (u32x4*)out, (u32x4*)out_f32, n16,
+                       slot_off, buf_bytes);
+  else
+    hipLaunchKernelGGL(pp_pull_kernel<false>, dim3(blocks), dim3(256), 0, st, slot, (u32x4*)out, (u32x4*)nullptr, n16,
+                       slot_off, buf_bytes);
   DTC_CHECK_LAUNCH();
   return 0;
 }

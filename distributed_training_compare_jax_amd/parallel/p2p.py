@@ -20,6 +20,9 @@ device — IPC within a device works the same way).
 Small messages (the vocab-parallel CE row statistics and label logits, the grad-norm scalar) take a
 one-shot variant (one barrier; every rank sums all peers' buffers itself), so a TP step issues no
 RCCL call at all: :class:`parallel.tp.TPComm` gathers by summing zero-padded slots.
+
+:class:`P2PPipe` (below) carries the pipeline stages' point-to-point messages over the same kind of buffer
+(``pp_comm: p2p``): sender-staged slots, epoch flags at the receiver, pulled by the receiver.
 """
 
 from __future__ import annotations
@@ -38,7 +41,7 @@ def _pci_bus_id(L, dev: int) -> str:
     return buf.value.decode().lower()
 
 
-def check_peer_access(L, rank: int, dev: int, peers) -> dict:
+def check_peer_access(L, rank: int, dev: int, peers, what: str = "P2P all-reduce", alt: str = "tp_comm: rccl") -> dict:
     """``peers``: [(rank, pci bus id)] of the group.  Every peer GPU must be reachable by direct
     loads from this one (hipDeviceCanAccessPeer over xGMI); raises naming the rank and peer
     otherwise — the P2P all-reduce never silently switches paths.  Peers on this same GPU (the
@@ -62,8 +65,8 @@ def check_peer_access(L, rank: int, dev: int, peers) -> dict:
         ok = ctypes.c_int(0)
         N.check(L.dtc_can_access_peer(dev, ordinal[bus], ctypes.byref(ok)), "hipDeviceCanAccessPeer")
         if not ok.value:
-            raise RuntimeError(f"P2P all-reduce: rank {rank} (GPU {dev}, {mine}) cannot access rank {p}'s GPU "
-                               f"({bus}) directly; use tp_comm: rccl")
+            raise RuntimeError(f"{what}: rank {rank} (GPU {dev}, {mine}) cannot access rank {p}'s GPU "
+                               f"({bus}) directly; use {alt}")
         out[p] = "xgmi"
     return out
 
@@ -219,6 +222,226 @@ class P2PAllReduce:
             raise RuntimeError(f"P2P all-reduce: rank {self.rank} buffer-half mismatch (device epoch "
                                f"{int(self.epoch.item())}, host calls {self.calls}): a captured graph with an odd "
                                "number of P2P calls was replayed; end every captured step with end_step()")
+
+    def close(self):
+        L = N.lib()
+        for q in self._opened:
+            L.dtc_p2p_close(ctypes.c_void_p(q))
+        self._opened = []
+        if self._own:
+            L.dtc_p2p_free(ctypes.c_void_p(self._own))
+            self._own = None
+
+
+# ------------------------------------------------------------------------------ pipeline stage messages
+# ``pp_comm: p2p`` (csrc/p2p.hip, "pipeline stage messages"): the f / b / s messages of parallel/pp.py as
+# stream-ordered kernels.  The sender stages a message into a slot of its OWN buffer and stores the step
+# epoch into a flag word of the receiver's buffer; the receiver waits on that word and pulls the slot.
+
+PP_SLOT_ALIGN = 256
+FLAG_WORDS = 1024  # csrc/p2p.hip FLAG_BYTES / 4
+
+
+class PPSlot(tuple):
+    """(peer, offset, nbytes, flag, buf_bytes, dtype name): ``peer`` = +1 / -1 (the next / previous stage);
+    ``offset`` = payload offset of the slot in the SENDER's buffer; ``flag`` = word index in the RECEIVER's flag
+    area; ``buf_bytes`` = payload bytes of the sender's buffer.  The same values on both ends of a message."""
+
+    __slots__ = ()
+    peer = property(lambda self: self[0])
+    offset = property(lambda self: self[1])
+    nbytes = property(lambda self: self[2])
+    flag = property(lambda self: self[3])
+    buf_bytes = property(lambda self: self[4])
+    dtype = property(lambda self: self[5])
+
+
+def _esize(dtype) -> int:
+    return torch.empty(0, dtype=dtype).element_size()
+
+
+def pp_slot_table(S: int, M: int, head_split: bool, msgs) -> list:
+    """The slot and flag layout of every stage, a pure function of (S, M, head split, message shapes and
+    dtypes), so every rank derives the same table (:class:`P2PPipe` exchanges its hash at init).
+
+    ``msgs``: {"f": (numel, dtype), "b": (numel, dtype)} plus, with the head split, "fh" (the final LayerNorm
+    output, the f message between the last two stages) and "s" (the packed row statistics, both ways).
+    One slot and one flag word per (direction, kind, microbatch).  Stage s's buffer holds its outgoing slots:
+    first those to s + 1 (f(0..M-1), then s(0..M-1) on stage S - 2 of a split head), then those to s - 1
+    (b(0..M-1), then s(0..M-1) on stage S - 1 of a split head), each aligned to 256 bytes.  Its flag words
+    count its incoming messages in the same order: from s - 1 first, then from s + 1.
+
+    Returns ``table[s] = {"send": {(kind, i): PPSlot}, "recv": {(kind, i): PPSlot}, "bytes": payload bytes,
+    "flags": flag words used}``; raises ValueError on a message that is not a multiple of 16 bytes or when a
+    stage needs more flag words than the 4096-byte flag area holds."""
+    if S < 2 or M < 1:
+        raise ValueError(f"P2P pipe: needs at least 2 stages and 1 microbatch (S={S}, M={M})")
+
+    def size(kind, a):  # message `kind` between stages a and a + 1
+        key = "fh" if (kind == "f" and head_split and a == S - 2) else kind
+        if key not in msgs:
+            raise ValueError(f"P2P pipe: no shape given for message kind {key!r}")
+        numel, dtype = msgs[key]
+        nb = int(numel) * _esize(dtype)
+        if nb <= 0 or nb % 16:
+            raise ValueError(f"P2P pipe: message {key!r} ({numel} x {dtype}) is {nb} bytes, not a positive multiple "
+                             "of 16 (the copy kernels move 16-byte pieces)")
+        return nb, str(dtype).replace("torch.", "")
+
+    out_up, out_dn = [], []  # per stage: [(kind, i, nbytes, dtype)] to s + 1 / to s - 1
+    for s in range(S):
+        up, dn = [], []
+        if s < S - 1:
+            up += [("f", i) + size("f", s) for i in range(M)]
+            if head_split and s == S - 2:
+                up += [("s", i) + size("s", s) for i in range(M)]
+        if s > 0:
+            dn += [("b", i) + size("b", s - 1) for i in range(M)]
+            if head_split and s == S - 1:
+                dn += [("s", i) + size("s", s - 1) for i in range(M)]
+        out_up.append(up)
+        out_dn.append(dn)
+    offs, total = [], []
+    for s in range(S):
+        o, cur = {}, 0
+        for d, lst in ((+1, out_up[s]), (-1, out_dn[s])):
+            for kind, i, nb, _ in lst:
+                o[(d, kind, i)] = cur
+                cur += (nb + PP_SLOT_ALIGN - 1) // PP_SLOT_ALIGN * PP_SLOT_ALIGN
+        offs.append(o)
+        total.append(cur)
+    table = [{"send": {}, "recv": {}, "bytes": total[s], "flags": 0} for s in range(S)]
+    for r in range(S):  # receiver r: flags for the messages from r - 1 (their "up" list), then from r + 1
+        k = 0
+        for src, d, lst in ((r - 1, +1, out_up[r - 1] if r > 0 else []), (r + 1, -1, out_dn[r + 1] if r + 1 < S else [])):
+            for kind, i, nb, dt in lst:
+                table[src]["send"][(kind, i)] = PPSlot((d, offs[src][(d, kind, i)], nb, k, total[src], dt))
+                table[r]["recv"][(kind, i)] = PPSlot((-d, offs[src][(d, kind, i)], nb, k, total[src], dt))
+                k += 1
+        if k > FLAG_WORDS:
+            raise ValueError(f"P2P pipe: stage {r} needs {k} flag words (one per direction, message kind and "
+                             f"microbatch; M={M}), the flag area holds {FLAG_WORDS}")
+        table[r]["flags"] = k
+    return table
+
+
+def pp_table_hash(S: int, M: int, head_split: bool, table) -> str:
+    import hashlib
+
+    rows = [(s, kind, sorted((k, tuple(v)) for k, v in t[kind].items())) for s, t in enumerate(table)
+            for kind in ("send", "recv")]
+    return hashlib.sha256(repr((S, M, bool(head_split), rows, [t["bytes"] for t in table])).encode()).hexdigest()
+
+
+class P2PPipe:
+    """The pipeline stage messages of one PP group as in-graph kernels (``TrainConfig.pp_comm: p2p``).
+
+    ``send`` / ``recv`` enqueue kernels on the current stream and return at once: nothing here calls the process
+    group after ``__init__``, so hipGraph capture records a stage's whole step, messages included.  The flag a
+    receive waits for carries the STEP EPOCH, a device counter :meth:`begin_step` bumps once per step (eager or
+    replayed), so all stages count steps alike with no host involvement.  A slot is rewritten one step after
+    it was read; that the schedule orders the rewrite after the read is what
+    ``parallel.pp.check_slot_reuse`` proves for every supported (schedule, S, M)."""
+
+    def __init__(self, group, stage: int, n_stages: int, device, n_micro: int, head_split: bool, msgs):
+        if not 2 <= n_stages <= 8:
+            raise ValueError(f"P2P pipe: {n_stages} stages; supports 2 to 8 (one xGMI hive)")
+        self.rank, self.world = stage, n_stages
+        self.device = torch.device(device)
+        full = pp_slot_table(n_stages, n_micro, head_split, msgs)
+        self.table = full[stage]
+        self._hash = pp_table_hash(n_stages, n_micro, head_split, full)
+        L = N.lib()
+        self._flag_bytes = int(L.dtc_p2p_flag_bytes())
+        assert self._flag_bytes == 4 * FLAG_WORDS
+        self.bytes = self.table["bytes"]
+        ptr = ctypes.c_void_p()
+        handle = ctypes.create_string_buffer(64)
+        with torch.cuda.device(self.device):
+            N.check(L.dtc_p2p_alloc(self._flag_bytes + max(self.bytes, 4096), ctypes.addressof(ptr),
+                                    ctypes.addressof(handle)), "dtc_p2p_alloc")
+        self._own = ptr.value
+        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        info = [None] * n_stages
+        dist.all_gather_object(info, (bytes(handle.raw), _pci_bus_id(L, dev), self._hash), group=group)
+        for p, (_, _, h) in enumerate(info):
+            if h != self._hash:
+                raise RuntimeError(f"P2P pipe: stage {stage} and stage {p} derived different slot tables "
+                                   f"({self._hash[:12]} vs {h[:12]}): their configurations differ")
+        near = [p for p in (stage - 1, stage + 1) if 0 <= p < n_stages]
+        self.peer_paths = check_peer_access(L, stage, dev, [(p, info[p][1]) for p in near], what="P2P pipe",
+                                            alt="pp_comm: rccl")
+        self._peer = {}
+        self._opened = []
+        with torch.cuda.device(self.device):
+            for p in near:
+                q = ctypes.c_void_p()
+                hb = ctypes.create_string_buffer(info[p][0], 64)
+                rc = L.dtc_p2p_open(ctypes.addressof(hb), ctypes.addressof(q))
+                if rc != 0:
+                    raise RuntimeError(f"P2P pipe: stage {stage} could not map stage {p}'s buffer (GPU {info[p][1]}): "
+                                       f"hipIpcOpenMemHandle error {rc}")
+                self._peer[p - stage] = q.value
+                self._opened.append(q.value)
+        self.epoch = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._flag_names = {v.flag: (k, v.peer) for k, v in self.table["recv"].items()}
+        # all stages' flag areas are zero before anyone's first signal can land
+        torch.cuda.synchronize(self.device)
+        dist.barrier(group=group)
+
+    def begin_step(self):
+        """Bump the step epoch; once per step, inside the step (so a replayed graph bumps it too)."""
+        N.check(N.lib().dtc_epoch_inc(self.epoch.data_ptr(), N.stream_ptr(self.device)), "dtc_epoch_inc")
+
+    def _entry(self, which, tag, i):
+        try:
+            return self.table[which][(tag, i)]
+        except KeyError:
+            raise KeyError(f"P2P pipe: stage {self.rank} has no {which} slot for message ({tag!r}, {i})") from None
+
+    def slot(self, tag: str, i: int):
+        """This stage's outgoing slot of message (tag, i) (an ``ops.gemm.RawOut``) for a producer that writes
+        it directly; :meth:`send` is then called with ``x=None``."""
+        from ..ops.gemm import RawOut
+
+        e = self._entry("send", tag, i)
+        return RawOut(self._own + self._flag_bytes + e.offset, getattr(torch, e.dtype), self.device)
+
+    def send(self, tag: str, i: int, x=None):
+        """Stage ``x`` (or nothing: the producer wrote :meth:`slot`) and signal the receiver.  Never waits."""
+        e = self._entry("send", tag, i)
+        if x is not None and (not x.is_contiguous() or x.numel() * x.element_size() != e.nbytes):
+            raise RuntimeError(f"P2P pipe: stage {self.rank} message ({tag!r}, {i}) is {tuple(x.shape)} {x.dtype}, "
+                               f"its slot holds {e.nbytes} contiguous bytes")
+        N.check(N.lib().dtc_pp_send(N.ptr(x), e.nbytes, self._own, e.offset, e.buf_bytes, self._peer[e.peer], e.flag,
+                                    self.epoch.data_ptr(), N.stream_ptr(self.device)), "dtc_pp_send")
+
+    def recv(self, tag: str, i: int, out: torch.Tensor, out_f32=None):
+        """Wait for this step's message (tag, i) and copy it into ``out``; ``out_f32``: also the fp32 image of
+        a bf16 message (exact), in the same pass."""
+        e = self._entry("recv", tag, i)
+        if not out.is_contiguous() or out.numel() * out.element_size() != e.nbytes:
+            raise RuntimeError(f"P2P pipe: stage {self.rank} destination of ({tag!r}, {i}) is {tuple(out.shape)} "
+                               f"{out.dtype}, the message is {e.nbytes} contiguous bytes")
+        if out_f32 is not None and (e.dtype != "bfloat16" or out_f32.dtype != torch.float32
+                                    or not out_f32.is_contiguous() or out_f32.numel() * 2 != e.nbytes):
+            raise RuntimeError(f"P2P pipe: stage {self.rank} fp32 image of ({tag!r}, {i}): needs a bf16 message and "
+                               f"a contiguous fp32 tensor of {e.nbytes // 2} elements")
+        N.check(N.lib().dtc_pp_recv(out.data_ptr(), N.ptr(out_f32), e.nbytes, self._peer[e.peer], e.offset,
+                                    e.buf_bytes, self._own, e.flag, self.epoch.data_ptr(), self.err.data_ptr(),
+                                    N.stream_ptr(self.device)), "dtc_pp_recv")
+
+    def describe(self, e: int) -> str:
+        (tag, i), peer = self._flag_names.get(e - 3000, (("?", -1), 0))
+        return (f"P2P pipe: stage {self.rank} timed out waiting for flag {e - 3000} (message ({tag!r}, {i}) from "
+                f"stage {self.rank + peer})")
+
+    def check(self):
+        """Raise if a receive timed out (its sender never signalled); call at a host sync point."""
+        e = int(self.err.item())
+        if e:
+            raise RuntimeError(self.describe(e))
 
     def close(self):
         L = N.lib()

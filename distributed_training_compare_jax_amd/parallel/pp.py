@@ -31,6 +31,12 @@ both directions at once.  :func:`simulate` replays the programs of all stages un
 semantics (per-pair ordered queues, rendezvous matching, groups atomic) and is run by the CPU tests
 for every S / M / schedule the engine accepts — no-deadlock and message order by construction.
 
+Transports: the programs above run over RCCL send/recv (``pp_comm: rccl``, host-staged on gloo), every run of
+post / wait items one eager call between two hipGraph segments, or over the in-graph kernels of
+:class:`parallel.p2p.P2PPipe` (``pp_comm: p2p``): sends never block, a receive completes once its send has
+been issued, and a stage's step is one graph.  That transport rewrites one slot per message every step;
+:func:`check_slot_reuse` proves the rewrite ordered after the neighbour's read for every schedule.
+
 Loss/gradient scaling is exact: each microbatch's CE is scaled by ``1/(mb·T·M)`` so the
 sum over microbatches is the full-batch mean (reference: ``psum(loss_sum / M)``, ``:187``).
 """
@@ -453,6 +459,104 @@ def simulate(kind: str, S: int, M: int, model: str = "pair", head_split: bool = 
             raise RuntimeError(f"{kind} S={S} M={M}: deadlock, stages blocked at {stuck}")
 
 
+def check_slot_reuse(kind: str, S: int, M: int, head_split: bool = False, progs=None, steps: int = 2) -> Dict[str, int]:
+    """Prove that the in-graph transport (``pp_comm: p2p``, :class:`parallel.p2p.P2PPipe`) never overwrites a
+    message slot before its reader has read it.
+
+    That transport keeps ONE slot per (sender, receiver, tag) in the sender's buffer, rewritten every step.
+    Its semantics: a send never blocks (stage the payload, signal); a receive completes -- at the ``wait`` of
+    the post that names it -- once the matching send of the same step has been issued, and only then reads the
+    sender's slot.  This replays ``steps`` consecutive steps of all stages' programs under those semantics with
+    vector clocks (program order within a stage, send -> completed receive across stages) and raises
+    RuntimeError if any write of a slot is not ordered, through those edges alone, after the read of the slot's
+    previous content -- in every execution, not just the replayed one.  A slot's write is dated at the last
+    compute item before its post, so the proof also covers a producer that writes the slot directly.  It also
+    raises on a deadlock and on a receive whose slot holds another step's message.
+
+    ``progs`` (one item list per stage) replaces the generated programs: the tests use it to show that the
+    check can fail.  Returns counters."""
+    if progs is None:
+        hk = {"head_split": True} if head_split else {}
+        progs = zb_programs(S, M, **hk) if kind == "zb" else [pp_program(kind, S, s, M, **hk) for s in range(S)]
+    S = len(progs)
+    what = f"{kind} S={S} M={M}" + (" head_split" if head_split else "")
+    items = [[(n, it) for n in range(steps) for it in progs[s]] for s in range(S)]
+    pc = [0] * S
+    vc = [[0] * S for _ in range(S)]  # vector clocks
+    dated: List = [None] * S          # the clock at the stage's last compute item
+    sent: Dict[tuple, List[int]] = {}  # (src, dst, tag, step) -> sender's clock at the send
+    last: Dict[tuple, list] = {}      # slot (src, dst, tag) -> [step of its content, reader's (stage, tick) | None]
+    posts: List[Dict[tuple, tuple]] = [dict() for _ in range(S)]
+    counts = {"writes": 0, "reads": 0, "reuses": 0}
+    while True:
+        progressed = False
+        for s in range(S):
+            while pc[s] < len(items[s]):
+                n, it = items[s][pc[s]]
+                if it[0] == "post":
+                    _, name, peer, snd, rcv = it
+                    dst = s + peer
+                    vc[s][s] += 1
+                    w = dated[s] if dated[s] is not None else vc[s]
+                    for tag in snd:
+                        slot = (s, dst, tag)
+                        prev = last.get(slot)
+                        if prev is not None:
+                            rd = prev[1]
+                            if rd is None or w[rd[0]] < rd[1]:
+                                raise RuntimeError(
+                                    f"{what}: slot reuse hazard: stage {s} rewrites its slot of message {tag} for "
+                                    f"stage {dst} in step {n} (post {name}) "
+                                    + ("before that stage has read" if rd is None else "with no message path from "
+                                       "that stage's read of") + f" the content of step {prev[0]}")
+                            counts["reuses"] += 1
+                        last[slot] = [n, None]
+                        sent[(s, dst, tag, n)] = list(vc[s])
+                        counts["writes"] += 1
+                    posts[s][(n, name)] = (dst, rcv)
+                elif it[0] == "wait":
+                    need = []
+                    for name in it[1]:
+                        if (n, name) not in posts[s]:
+                            raise RuntimeError(f"{what}: stage {s} waits for {name}, which it has not posted")
+                        dst, rcv = posts[s][(n, name)]
+                        need += [(dst, s, tag, n) for tag in rcv]
+                    if not all(k in sent for k in need):
+                        break
+                    for k in need:
+                        slot = k[:3]
+                        if last[slot][0] != n or last[slot][1] is not None:
+                            raise RuntimeError(f"{what}: stage {s} reads message {k[2]} of step {n} from stage {k[0]}, "
+                                               f"whose slot holds step {last[slot][0]}"
+                                               + (" (already read)" if last[slot][1] is not None else ""))
+                        vc[s] = [max(a, b) for a, b in zip(vc[s], sent[k])]
+                        vc[s][s] += 1
+                        last[slot][1] = (s, vc[s][s])
+                        counts["reads"] += 1
+                    for name in it[1]:
+                        posts[s].pop((n, name))
+                else:
+                    dated[s] = list(vc[s])
+                pc[s] += 1
+                progressed = True
+        if all(pc[s] == len(items[s]) for s in range(S)):
+            unread = sorted(k for k, v in last.items() if v[1] is None)
+            if unread:
+                raise RuntimeError(f"{what}: messages never received: {unread}")
+            return counts
+        if not progressed:
+            stuck = {s: items[s][pc[s]] for s in range(S) if pc[s] < len(items[s])}
+            raise RuntimeError(f"{what}: deadlock under non-blocking sends, stages blocked at {stuck}")
+
+
+def graph_cuts(kind: str, S: int, s: int, M: int, head_split: bool = False) -> int:
+    """Graph cuts the eager transports make in stage s's pipeline: one per run of post / wait items between two
+    compute items (``run_pipeline``'s ``run_comm`` calls).  The in-graph transport makes none."""
+    prog = pp_program(kind, S, s, M, head_split=head_split)
+    return sum(1 for k, it in enumerate(prog)
+               if it[0] in ("post", "wait") and (k == 0 or prog[k - 1][0] not in ("post", "wait")))
+
+
 # ------------------------------------------------------------------------------ executor
 class _HostSend:
     """isend of a device tensor through a host copy (gloo backend); ``wait()`` like a Work."""
@@ -570,6 +674,33 @@ def run_pipeline(eng) -> None:
         # PP point-to-point stays eager between segments (RCCL p2p inside a capture is unexercised here)
         prog.comm(fn, sig=sig, capturable=False)
 
+    pipe = getattr(eng, "pp_pipe", None)  # pp_comm: p2p -- the messages as kernels on the compute stream
+
+    def run_comm_p2p(run):
+        """The in-graph transport (``parallel.p2p.P2PPipe``): a post sends each of its send tags (stage copy +
+        flag store, never waits; its receives need nothing yet), a wait pulls each receive tag of the posts it
+        names, in program order (waiting for a send is a no-op).  No ``prog.comm``: capture records these
+        launches like any other kernel, so the stage's step is not cut.  A received bf16 message gets its
+        fp32 image in the same pass (the cast the F / B items otherwise launch)."""
+        for it in run:
+            if it[0] == "post":
+                for tag in it[3]:
+                    pipe.send(tag[0], tag[1], tensor_of(tag, True))
+                    if tag[0] != "s":  # the copy is queued: drop the stage's reference, as release() does
+                        (outs if tag[0] == "f" else dx_out).pop(tag[1], None)
+                continue
+            for n in it[1]:
+                for tag in rcv_tags[n]:
+                    d, i = tag
+                    f32 = None
+                    if bf and d != "s" and not (d == "f" and head_b):
+                        f32 = eng.recv_x[i] if d == "f" else eng.recv_dx[i]
+                    pipe.recv(d, i, tensor_of(tag, False), f32)
+
+    if pipe is not None:
+        run_comm = run_comm_p2p
+        pipe.begin_step()
+
     kind = eng.tcfg.pp_schedule
     zb = kind == "zb"
     items = pp_program(kind, S, s, M, costs=eng.pp_item_costs() if zb else None, head_split=hs,
@@ -577,6 +708,7 @@ def run_pipeline(eng) -> None:
     wq: Dict[int, list] = {}  # zb: microbatch -> its queued weight gradients (run by its W item)
     n_w_done = 0
     sent_tags = {it[1]: it[3] for it in items if it[0] == "post"}  # post name -> tags it sends
+    rcv_tags = {it[1]: it[4] for it in items if it[0] == "post"}  # post name -> tags it receives
     dx_out: Dict[int, torch.Tensor] = {}
     k = 0
     while k < len(items):
@@ -607,7 +739,7 @@ def run_pipeline(eng) -> None:
             k += 1
             continue
         if kind == "F":
-            if not first and bf:
+            if not first and bf and pipe is None:  # (the in-graph receive wrote the fp32 image itself)
                 cast_bf16_to_f32(eng.recv_x_bf[i], eng.recv_x[i])
             h = st.embed_forward(ids, step, row0, ctx) if first else eng.recv_x[i]
             h = st.stage_forward(h, rows, ctx)
@@ -631,7 +763,8 @@ def run_pipeline(eng) -> None:
                 dx = eng.recv_dx[i]
                 dx_c = eng.recv_dx_c[i]
                 if bf:  # the received bf16 image is the compute-dtype copy; the fp32 one is cast from it
-                    cast_bf16_to_f32(eng.recv_dx_bf[i], dx)
+                    if pipe is None:
+                        cast_bf16_to_f32(eng.recv_dx_bf[i], dx)
                     if dx_c is not dx:
                         dx_c = eng.recv_dx_bf[i]
                 elif dx_c is not dx and not head_a:

@@ -41,6 +41,22 @@ class Engine:
         self.dinfo = dinfo
         self.device = dinfo.device
         dp, tp, pp = resolve_degrees(train_cfg.parallel, dinfo.world, train_cfg.dp, train_cfg.tp, train_cfg.pp)
+        # pp_comm: p2p (the stage messages, the PP loss sum and the pp_clip: global norm as in-graph kernels over
+        # IPC-mapped buffers, parallel/p2p.py P2PPipe): what it does not cover is refused here, before any collective
+        if train_cfg.pp_comm not in ("rccl", "p2p"):
+            raise ValueError(f"pp_comm={train_cfg.pp_comm!r}: expected 'rccl' or 'p2p'")
+        if train_cfg.pp_comm == "p2p":
+            why = None
+            if pp == 1:
+                why = "pp == 1 (there are no stage messages)"
+            elif dinfo.device.type != "cuda":
+                why = "a CPU device (the transport is HIP kernels over IPC-mapped device buffers)"
+            elif pp > 8:
+                why = f"pp={pp} (the peer buffers span one xGMI hive: at most 8 stages)"
+            elif tp > 1:
+                why = f"tp={tp} (out of scope: the TP and the PP peer buffers have not been run together; use tp = 1)"
+            if why:
+                raise ValueError(f"pp_comm: p2p cannot be combined with {why}")
         # lm_head + CE split by vocab over the last two pipeline stages (models/gpt.py head_split_*): auto when
         # the head alone outweighs an even share of the model (GPT-2 small at pp >= 5: 2.9 blocks vs 14.9 / pp)
         hsplit = train_cfg.pp_head_split
@@ -149,6 +165,8 @@ class Engine:
         # (parallel/dist.py explains the ordering argument)
         self.program.sync_comms = bool(on_gpu and dinfo.backend == "gloo" and (dinfo.world > 1 or self.dp_comm))
         self.p2p = None
+        self.pp_pipe = None  # pp_comm: p2p -- the stage messages (created with the message buffers below)
+        self.pp_ar = None    # ... and the PP group's scalar sums (loss, pp_clip: global norm)
         mode = train_cfg.tp_comm
         if tp > 1 and on_gpu and (mode == "p2p" or (mode == "auto" and dinfo.backend == "nccl")):
             from ..parallel.p2p import P2PAllReduce
@@ -305,6 +323,8 @@ class Engine:
                 mk = lambda: [torch.zeros(self.mb_rows * T, D, dtype=torch.bfloat16, device=self.device)
                               for _ in range(self.n_micro)]
                 self.send_x_bf, self.send_dx_bf, self.recv_x_bf, self.recv_dx_bf = mk(), mk(), mk(), mk()
+            if train_cfg.pp_comm == "p2p":
+                self._init_pp_p2p(pp)
         self.steps_done = 0
         # Deferred optimizer (pp == 1, GPU): the step ends with the global norm and the AdamW of
         # the embedding tables only; the rest of the update runs at the START of the next step
@@ -359,6 +379,40 @@ class Engine:
             self._reserve_workspaces()
 
     # ------------------------------------------------------------------ helpers
+    def _init_pp_p2p(self, pp: int):
+        """``pp_comm: p2p``: the stage messages as in-graph kernels (:class:`parallel.p2p.P2PPipe`; the ``recv_*``
+        buffers stay the receive destinations, so every replay moves the same addresses) and a small
+        :class:`parallel.p2p.P2PAllReduce` on the PP group for the loss sum and the ``pp_clip: global`` norm
+        (scalars padded to 4 floats by :class:`parallel.tp.TPComm`; a rank-order fp32 sum, identical on
+        every stage).  With dp == 1 a stage's step then holds no process-group collective at all."""
+        from ..parallel.p2p import P2PAllReduce, P2PPipe
+        from ..parallel.pp import check_slot_reuse, pp_program, zb_programs
+
+        # the programs this run will execute (zb: placed with this model's costs) must order every slot rewrite
+        # after the neighbour's read; deterministic, so every rank raises alike
+        kind, hs = self.tcfg.pp_schedule, self.pp_head_split
+        progs = (zb_programs(pp, self.n_micro, self.pp_item_costs(), self.pp_comm_costs(), head_split=hs)
+                 if kind == "zb" else [pp_program(kind, pp, s, self.n_micro, head_split=hs) for s in range(pp)])
+        check_slot_reuse(kind, pp, self.n_micro, hs, progs=progs)
+        m, n = self.mesh, self.mb_rows * self.T * self._D
+        mdt = torch.bfloat16 if self.pp_bf16 else torch.float32
+        msgs = {"f": (n, mdt), "b": (n, mdt)}
+        if self.pp_head_split:
+            msgs["fh"] = (n, self.act_dtype)
+            msgs["s"] = (self.mb_rows * self.T * 3, torch.float32)
+        self.pp_pipe = P2PPipe(m.pp_group, m.pp_idx, pp, self.device, self.n_micro, self.pp_head_split, msgs)
+        self.pp_ar = P2PAllReduce(m.pp_group, m.pp_idx, pp, self.device, 4096)
+        self.pp_sum = TPComm(m.pp_group, pp, m.pp_idx, self.program, p2p=self.pp_ar)
+        self.opt.pp_comm = self.pp_sum
+
+    def close(self):
+        """Release the peer-to-peer transports (IPC mappings and their uncached buffers)."""
+        for name in ("pp_pipe", "pp_ar", "p2p"):
+            t = getattr(self, name, None)
+            if t is not None:
+                t.close()
+                setattr(self, name, None)
+
     def _wgrad_group_for_memory(self, mc: ModelConfig, n_layers: int) -> int:
         """Auto ``wgrad_group`` at dp == 1: one grouped launch for the whole stage (0) keeps every layer's
         weight-gradient operands alive until the end of the backward -- per layer the bf16 dY tensors
@@ -638,6 +692,12 @@ class Engine:
         if not groups:
             return []
         t = self.loss
+        if self.pp_ar is not None and m.pp > 1 and pp:
+            # pp_comm: p2p -- the PP sum is an in-graph kernel (the other stages hold zeros: exact in any order)
+            self.pp_sum.all_reduce_(t)
+            groups = [g for g in groups if g is not m.pp_group]
+            if not groups:
+                return []
         if name is None:
             for g in groups:
                 self.program.comm(lambda g=g: dist.all_reduce(t, group=g), sig=csig("all_reduce", g, t))
@@ -656,7 +716,9 @@ class Engine:
     def _step_fn_pp(self):
         from ..parallel.pp import run_pipeline
 
-        with self._CommSafeGemms(self.stage.flat.device.type == "cuda"):  # send/recv overlap compute
+        # send/recv overlap compute.  Kept under pp_comm: p2p too, where no RCCL kernel holds CUs: dropping it
+        # there changes GEMM plans and waits for an A/B on hardware (docs/CAPTURE.md)
+        with self._CommSafeGemms(self.stage.flat.device.type == "cuda"):
             run_pipeline(self)
         self.buckets.ready_all()
         # the loss sum overlaps the bucket all-reduces and the optimizer; joined at the very end
@@ -671,6 +733,8 @@ class Engine:
         out = self._step_fn_pp() if self.mesh.pp > 1 else self._step_fn_dp_tp()
         if self.p2p is not None:
             self.p2p.end_step()  # even P2P calls per step: every call site keeps its buffer half on replay
+        if self.pp_ar is not None:
+            self.pp_ar.end_step()
         return out
 
     # ------------------------------------------------------------------ public
@@ -735,6 +799,9 @@ class Engine:
         row statistics).  Blocking: call outside pipelined loops."""
         if self.p2p is not None:
             self.p2p.check()
+        if self.pp_pipe is not None:
+            self.pp_pipe.check()
+            self.pp_ar.check()
         if self.stage.ln_sync is not None:
             self.stage.ln_sync.check()
 
@@ -745,6 +812,9 @@ class Engine:
         out = []
         if self.p2p is not None:
             out.append(("p2p", self.p2p.err))
+        if self.pp_pipe is not None:
+            out.append(("pp_pipe", self.pp_pipe.err))
+            out.append(("pp_ar", self.pp_ar.err))
         if self.stage.ln_sync is not None:
             out.append(("ln", self.stage.ln_sync.err))
         return out
@@ -784,6 +854,11 @@ class Engine:
             if e:
                 if name == "p2p":
                     raise RuntimeError(f"P2P all-reduce: rank {self.p2p.rank} timed out waiting for rank {e - 1000}")
+                if name == "pp_pipe":
+                    raise RuntimeError(self.pp_pipe.describe(e))
+                if name == "pp_ar":
+                    raise RuntimeError(f"P2P all-reduce (PP group): stage {self.pp_ar.rank} timed out waiting for "
+                                       f"stage {e - 1000}")
                 raise RuntimeError("fused LayerNorm: a row-statistics wait timed out (outputs were NaN)")
         return float(slot.item()) / self.mesh.dp
 

@@ -84,6 +84,7 @@ class FusedAdamW:
         self._done = []
         self.reducer = None  # GradReducer of the model stage (single-stream GPU backward)
         self.tp_comm = None  # parallel.tp.TPComm: the TP norm partial through its P2P path when it has one
+        self.pp_comm = None  # pp_comm: p2p -- the PP group's sums as in-graph kernels (a TPComm over that group)
         self._fused = ([], 0)  # flat ranges whose Σg² arrives precomputed (set_fused_sumsq), slot count
         self._cuts = None
         self.fused_part = None
@@ -186,7 +187,9 @@ class FusedAdamW:
                 g = self.tp_group
                 s = self.sumsq
                 self.program.comm(lambda: dist.all_reduce(s, group=g), sig=csig("all_reduce", g, s))
-        if self.pp_group is not None:
+        if self.pp_group is not None and self.pp_comm is not None:
+            self.pp_comm.all_reduce_(self.sumsq)  # in-graph one-shot, rank-order fp32 sum (no graph cut)
+        elif self.pp_group is not None:
             g = self.pp_group
             s = self.sumsq
             self.program.comm(lambda: dist.all_reduce(s, group=g), sig=csig("all_reduce", g, s))

@@ -33,9 +33,12 @@ def _run(train_config_path: str, model_config_path: str, optim_config_path: str,
     dinfo = init_distributed(train_config.device)
     if dinfo.rank == 0:
         print(f"Running `{train_config.parallel}` on {dinfo.world} devices.", flush=True)
+    result = None
     try:
-        train(train_config, model_config, opt_config, dinfo)
+        result = train(train_config, model_config, opt_config, dinfo)
     finally:
+        if result is not None:
+            result["engine"].close()  # the peer-to-peer transports' IPC mappings and buffers
         destroy()
 
 
