@@ -45,7 +45,12 @@ are optional and default to the reference behaviour:
   ``dp_comm`` (``rccl`` | ``p2p``: the DP gradient buckets, the loss sum and the embedding-gradient gather as
   process-group collectives, or as in-graph peer-to-peer kernels on one comm stream forked inside the step,
   ``parallel/p2p.py P2PGradReduce``: a pure-DP step is one hipGraph; GPU, 2 <= dp <= 8 or the dp = 1
-  rehearsal, tp = pp = 1, zero_stage = 0; default ``rccl``).
+  rehearsal, tp = pp = 1, zero_stage = 0; default ``rccl``),
+  ``zero_comm`` (``rccl`` | ``p2p``, with ``zero_stage: 1``: ``ShardedAdamW``'s exposed process-group reduce-scatter
+  and all-gather, or the DP buckets reduce-scattered under the backward, the AdamW on the owned slices and a
+  per-bucket parameter gather that also writes the bf16 mirror, all in-graph peer-to-peer kernels,
+  ``parallel/p2p.py P2PZeroShard`` + ``train/optimizer.py P2PShardedAdamW``: one hipGraph per step, ``dp_grad_dtype``
+  honoured; GPU, 2 <= dp <= 8 or the dp = 1 rehearsal, tp = pp = 1, ``dp_comm: rccl``; default ``rccl``).
 """
 
 from __future__ import annotations
@@ -167,6 +172,15 @@ class TrainConfig:
     # zero_stage == 0, 2 <= dp <= 8 (dp == 1 only with dp_comm_rehearsal).  No auto: the default stays rccl until
     # p2p has run across real GPUs (docs/CAPTURE.md)
     dp_comm: str = "rccl"
+    # rccl | p2p: the transport of the SHARDED optimizer step (zero_stage: 1; dp_comm names that of the replicated
+    # one and stays rccl).  rccl = ShardedAdamW: one reduce-scatter after the backward and one all-gather after the
+    # update through the process group, both exposed, then a full fp32 -> bf16 mirror cast.  p2p = the gradient
+    # buckets reduce-scattered under the backward as stream-ordered kernels over IPC-mapped peer buffers
+    # (parallel/p2p.py P2PZeroShard), AdamW on the owned slices (train/optimizer.py P2PShardedAdamW), per-bucket
+    # parameter gathers that write the bf16 mirror in the same pass: ONE hipGraph per step, no eager collective,
+    # dp_grad_dtype honoured.  GPU only, tp == pp == 1, 2 <= dp <= 8 (dp == 1 only with dp_comm_rehearsal).  No
+    # auto: the default stays rccl until p2p has run across real GPUs (docs/CAPTURE.md)
+    zero_comm: str = "rccl"
     # fp32 | bf16 | auto: TP row-parallel / input-gradient partials (fp32 sums either way); auto = bf16 when the
     # compute dtype is bf16 (5000-step tp2 curve: the same gap to dp1 as fp32, profiles/r5_cross_strategy.md)
     tp_comm_dtype: str = "auto"

@@ -464,6 +464,163 @@ __global__ void __launch_bounds__(256) dp_gather_kernel(PeerTable t, int world, 
   }
 }
 
+// ---------------------------------------------------------------- ZeRO-1 over the DP buckets (zero_comm: p2p)
+// The bucket all-reduce above cut in the middle: the sharded AdamW sits on the reduced slice, and the gather moves
+// the updated parameters instead of the gradients.
+//
+//   reduce-scatter   pack (dp_pack_kernel, as is) -> barrier (+2) -> dp_reduce_shard_kernel: the loads and the sums
+//                    of dp_reduce_kernel, but the result goes as fp32 straight into grads[own slice] (bf16 widened
+//                    exactly), so those elements hold bit for bit what dtc_dp_allreduce would have left there, and
+//                    the slice's sum of squares goes to one partial per block (fixed order: per thread in loop
+//                    order, the wave by xor shuffles, the 4 waves through LDS in wave order; no atomics)
+//   parameter gather pack of the owned fp32 parameter slice, compact at the start of the half -> barrier (+2) ->
+//                    dp_gather_params_kernel: every 4-float group of the bucket from its owner (own slice: local
+//                    memory, not rewritten), written to params and, rounded like cast_kernel, to the bf16 mirror
+//
+// ONE barrier per call is enough.  A call only READS the peers' halves after its barrier (it writes local memory),
+// the halves alternate per call and every call advances the epoch by 2.  Call k + 2 rewrites half h only after this
+// rank passed call k + 1's barrier; a rank signals that barrier only after its call-k kernels have finished reading
+// half h, because the barrier kernel follows them in stream order.  This needs every call of the object in ONE
+// stream order on every rank, which is how parallel/p2p.py issues them (P2PGradReduce.on_comm: one comm stream,
+// forked from and joined to the step's stream by events; or the step's stream itself).  The two-barrier calls of
+// the object (dtc_dp_allreduce, the two-shot sum) and the one-barrier ones mix freely under the same argument: a
+// half is written remotely by nobody, and locally only before the call's first barrier or, in the two-shot
+// reduction, between its two barriers by its owner alone.
+template <bool BF16>
+__global__ void __launch_bounds__(256) dp_reduce_shard_kernel(PeerTable t, int rank, int world, long n, long pieces,
+                                                              long half_bytes, float* __restrict__ grads,
+                                                              float* __restrict__ part,
+                                                              const uint32_t* __restrict__ epoch) {
+  using V = typename std::conditional<BF16, bf16x8, f32x4>::type;
+  const int h = ((epoch[0] - 2) >> 1) & 1;  // the call's one barrier (+2) has passed since the pack
+  const long chunk = (pieces + world - 1) / world;
+  const long lo = min(pieces, rank * chunk), hi = min(pieces, lo + chunk);
+  const long off = FLAG_BYTES + h * half_bytes;
+  DTC_ASSERT(world >= 1 && world <= P2P_MAX && rank >= 0 && rank < world && n > 0 && n % 4 == 0 &&
+             pieces == (BF16 ? (n + 7) / 8 : n / 4) && 16 * pieces <= half_bytes && chunk * world >= pieces &&
+             lo <= hi && hi <= pieces);
+  f32x4* g4 = (f32x4*)grads;
+  float sq = 0.f;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i0 = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < hi; i0 += DP_RU * stride) {
+    V v[DP_RU][P2P_MAX];
+#pragma unroll
+    for (int u = 0; u < DP_RU; ++u) {
+      const long i = i0 + u * stride;
+      if (i < hi) {
+#pragma unroll
+        for (int p = 0; p < P2P_MAX; ++p)
+          if (p < world) v[u][p] = ((const V*)(t.base[p] + off))[i];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < DP_RU; ++u) {
+      const long i = i0 + u * stride;
+      if (i < hi) {
+        if constexpr (BF16) {
+          float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int p = 0; p < P2P_MAX; ++p)
+            if (p < world) add8(a, v[u][p]);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) a[e] = (float)f2bf(a[e]);  // one rounding; the widening is exact
+          DTC_ASSERT(8 * i + 4 <= n);
+          g4[2 * i] = f32x4{a[0], a[1], a[2], a[3]};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sq = fmaf(a[e], a[e], sq);
+          if (8 * i + 4 < n) {  // the last piece of n % 8 == 4 holds 4 elements: never write past grads + n
+            g4[2 * i + 1] = f32x4{a[4], a[5], a[6], a[7]};
+#pragma unroll
+            for (int e = 4; e < 8; ++e) sq = fmaf(a[e], a[e], sq);
+          }
+        } else {
+          f32x4 s = v[u][0];
+#pragma unroll
+          for (int p = 1; p < P2P_MAX; ++p)
+            if (p < world) s += v[u][p];
+          DTC_ASSERT(4 * i + 4 <= n);
+          g4[i] = s;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sq = fmaf(s[e], s[e], sq);
+        }
+      }
+    }
+  }
+  // one partial per block, every block (an empty slice: zeros)
+  __shared__ float wsum[4];
+  sq = warp_sum(sq);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// 4-float groups [q_lo, q_hi) of params -> the start of own half h (the slice this rank owns and has just updated)
+__global__ void __launch_bounds__(256) dp_pack_params_kernel(const float* __restrict__ params, PeerTable t, int rank,
+                                                             long q_lo, long q_hi, long half_bytes,
+                                                             const uint32_t* __restrict__ epoch) {
+  const int h = (epoch[0] >> 1) & 1;
+  DTC_ASSERT(rank >= 0 && rank < P2P_MAX && 0 <= q_lo && q_lo <= q_hi && 16 * (q_hi - q_lo) <= half_bytes);
+  f32x4* dst = (f32x4*)(t.base[rank] + FLAG_BYTES + h * half_bytes);
+  const f32x4* p4 = (const f32x4*)params + q_lo;
+  const long nq = q_hi - q_lo;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < nq; i0 += DP_U * stride) {
+    f32x4 a[DP_U];
+#pragma unroll
+    for (int u = 0; u < DP_U; ++u) {
+      const long i = i0 + u * stride;
+      if (i < nq) a[u] = p4[i];
+    }
+#pragma unroll
+    for (int u = 0; u < DP_U; ++u) {
+      const long i = i0 + u * stride;
+      if (i < nq) dst[i] = a[u];
+    }
+  }
+}
+
+// params[4-float group i] = the group of its owner (piece i / qpp belongs to rank piece / chunk; that rank's slice
+// sits compact at the start of its half); own groups are read from params.  mirror[4 i .. 4 i + 3] = bf16 of the
+// same values for 4 i < n_mirror.  Nothing is written at or behind params + n or mirror + n_mirror.
+__global__ void __launch_bounds__(256) dp_gather_params_kernel(PeerTable t, int rank, int world, long n, long pieces,
+                                                               int qpp, long half_bytes, float* __restrict__ params,
+                                                               bf16* __restrict__ mirror, long n_mirror,
+                                                               const uint32_t* __restrict__ epoch) {
+  const int h = ((epoch[0] - 2) >> 1) & 1;
+  const long chunk = (pieces + world - 1) / world;
+  const long off = FLAG_BYTES + h * half_bytes;
+  const long nq = n / 4;
+  DTC_ASSERT(world >= 1 && world <= P2P_MAX && rank >= 0 && rank < world && n > 0 && n % 4 == 0 &&
+             (qpp == 1 || qpp == 2) && pieces == (nq + qpp - 1) / qpp && n_mirror >= 0 && n_mirror <= n &&
+             n_mirror % 4 == 0 && 16 * min(nq, chunk * qpp) <= half_bytes);
+  f32x4* p4 = (f32x4*)params;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < nq; i0 += DP_U * stride) {
+    f32x4 v[DP_U];
+    bool own[DP_U];
+#pragma unroll
+    for (int u = 0; u < DP_U; ++u) {
+      const long i = i0 + u * stride;
+      own[u] = true;
+      if (i < nq) {
+        const int q = (int)((i / qpp) / chunk);
+        DTC_ASSERT(q >= 0 && q < world && i >= q * chunk * qpp && 16 * (i - q * chunk * qpp + 1) <= half_bytes);
+        own[u] = q == rank;
+        v[u] = own[u] ? p4[i] : ((const f32x4*)(t.base[q] + off))[i - q * chunk * qpp];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < DP_U; ++u) {
+      const long i = i0 + u * stride;
+      if (i < nq) {
+        if (!own[u]) p4[i] = v[u];
+        if (4 * i < n_mirror)
+          *(bf16x4*)(mirror + 4 * i) = bf16x4{f2bf(v[u][0]), f2bf(v[u][1]), f2bf(v[u][2]), f2bf(v[u][3])};
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- intra-device stream flags
 // Cross-stream dependencies between two separately captured hipGraphs (main / side) on the SAME
 // device: a producer stream bumps flags[k] to its replay epoch (agent-scope release, after all of
@@ -796,6 +953,80 @@ int dtc_dp_allreduce(float* grads, long n, int bf16, void* const* bases, int ran
   else
     hipLaunchKernelGGL(dp_gather_kernel<false>, dim3(blocks), dim3(256), 0, st, t, world, n, pieces, half_bytes, grads,
                        epoch);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- ZeRO-1 over the DP buckets (kernels above).  Both calls: epoch + 2, one barrier.
+// Blocks (= Σg² partial slots) of the reduce-scatter of an n-element bucket; the same on every rank.
+int dtc_dp_rs_slots(long n, int bf16, int world, int max_blocks) {
+  if (n <= 0 || n % 4 || world < 1 || world > P2P_MAX || max_blocks < 1 || max_blocks > 1024) return -1;
+  const long pieces = bf16 ? (n + 7) / 8 : n / 4;
+  const long chunk = (pieces + world - 1) / world;
+  return (int)std::min((long)max_blocks, std::max(1L, (chunk + 255) / 256));
+}
+
+// grads[own slice] (fp32, in place) = sum over ranks of grads[own slice], where the own slice of the n-element
+// bucket is pieces [min(pieces, rank chunk), min(pieces, (rank + 1) chunk)) of 4 fp32 / 8 bf16 elements, chunk =
+// ceil(pieces / W): the values dtc_dp_allreduce leaves there.  Nothing else of grads is written.  part[0 : nslots]
+// (nslots == dtc_dp_rs_slots(...)) = per-block partial sums of squares of the slice (zeros for an empty one).
+int dtc_dp_reduce_scatter(float* grads, long n, int bf16, float* part, int nslots, void* const* bases, int rank,
+                          int world, long half_bytes, uint32_t* epoch, int* err, int max_blocks, hipStream_t st) {
+  if (!grads || !part || !bases || !epoch || !err || world < 1 || world > P2P_MAX || rank < 0 || rank >= world ||
+      n <= 0 || n % 4 || ((uintptr_t)grads & 15) || ((uintptr_t)part & 3) || max_blocks < 1 || max_blocks > 1024 ||
+      half_bytes <= 0 || half_bytes % 16)
+    return 4001;
+  const long pieces = bf16 ? (n + 7) / 8 : n / 4;
+  if (pieces > half_bytes / 16 || nslots != dtc_dp_rs_slots(n, bf16, world, max_blocks)) return 4001;
+  PeerTable t;
+  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
+  const int blocks = (int)std::min((long)max_blocks, std::max(1L, (pieces + 255) / 256));
+  if (bf16)
+    hipLaunchKernelGGL(dp_pack_kernel<true>, dim3(blocks), dim3(256), 0, st, grads, t, rank, n, pieces, half_bytes,
+                       epoch);
+  else
+    hipLaunchKernelGGL(dp_pack_kernel<false>, dim3(blocks), dim3(256), 0, st, grads, t, rank, n, pieces, half_bytes,
+                       epoch);
+  DTC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
+  DTC_CHECK_LAUNCH();
+  if (bf16)
+    hipLaunchKernelGGL(dp_reduce_shard_kernel<true>, dim3(nslots), dim3(256), 0, st, t, rank, world, n, pieces,
+                       half_bytes, grads, part, epoch);
+  else
+    hipLaunchKernelGGL(dp_reduce_shard_kernel<false>, dim3(nslots), dim3(256), 0, st, t, rank, world, n, pieces,
+                       half_bytes, grads, part, epoch);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+// params[0:n] (fp32, one bucket) = every rank's owned slice of it (the ownership of dtc_dp_reduce_scatter with the
+// same n, bf16 and world; bf16 only selects that plan, the parameters travel as fp32), own slice untouched;
+// mirror[0:n_mirror] (bf16, optional, n_mirror <= n) = the rounded parameters, in the same pass.  Grids of at most
+// max_blocks (1 .. 1024; the step's tail, nothing overlaps it: the caller passes 1024).
+int dtc_dp_param_gather(float* params, bf16* mirror, long n, long n_mirror, int bf16_plan, void* const* bases,
+                        int rank, int world, long half_bytes, uint32_t* epoch, int* err, int max_blocks,
+                        hipStream_t st) {
+  if (!params || !bases || !epoch || !err || world < 1 || world > P2P_MAX || rank < 0 || rank >= world || n <= 0 ||
+      n % 4 || ((uintptr_t)params & 15) || ((uintptr_t)mirror & 7) || n_mirror < 0 || n_mirror > n || n_mirror % 4 ||
+      (n_mirror > 0 && !mirror) || max_blocks < 1 || max_blocks > 1024 || half_bytes <= 0 || half_bytes % 16)
+    return 4001;
+  const int qpp = bf16_plan ? 2 : 1;
+  const long nq = n / 4, pieces = (nq + qpp - 1) / qpp;
+  const long chunk = (pieces + world - 1) / world;
+  if (std::min(nq, chunk * qpp) > half_bytes / 16) return 4001;  // the largest slice (rank 0's) must fit the half
+  const long q_lo = std::min(nq, rank * chunk * qpp), q_hi = std::min(nq, q_lo + chunk * qpp);
+  PeerTable t;
+  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
+  const int pk = (int)std::min((long)max_blocks, std::max(1L, (q_hi - q_lo + 255) / 256));
+  hipLaunchKernelGGL(dp_pack_params_kernel, dim3(pk), dim3(256), 0, st, params, t, rank, q_lo, q_hi, half_bytes,
+                     epoch);
+  DTC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
+  DTC_CHECK_LAUNCH();
+  const int blocks = (int)std::min((long)max_blocks, std::max(1L, (nq + 255) / 256));
+  hipLaunchKernelGGL(dp_gather_params_kernel, dim3(blocks), dim3(256), 0, st, t, rank, world, n, pieces, qpp,
+                     half_bytes, params, mirror, n_mirror, epoch);
   DTC_CHECK_LAUNCH();
   return 0;
 }

@@ -153,6 +153,9 @@ def _declare(lib):
         "dtc_p2p_reduce_scatter": ([vp, i, vp, l, vp, i, i, l, vp, vp, vp, vp, i, vp], i),
         "dtc_p2p_all_gather": ([vp, vp, l, vp, i, i, l, vp, vp, vp], i),
         "dtc_dp_allreduce": ([vp, l, i, vp, i, i, l, vp, vp, i, vp], i),
+        "dtc_dp_rs_slots": ([l, i, i, i], i),
+        "dtc_dp_reduce_scatter": ([vp, l, i, vp, i, vp, i, i, l, vp, vp, i, vp], i),
+        "dtc_dp_param_gather": ([vp, vp, l, l, i, vp, i, i, l, vp, vp, i, vp], i),
         "dtc_pp_send": ([vp, l, vp, l, l, vp, i, vp, vp], i),
         "dtc_pp_recv": ([vp, vp, l, vp, l, l, vp, i, vp, vp, vp], i),
         "dtc_cu_hog": ([i, l, i, vp, vp], i),

@@ -53,7 +53,8 @@ class GradBuckets:
 
     ``transport``: ``rccl`` issues each bucket through ``program.comm`` (a process-group collective);
     ``p2p`` (``TrainConfig.dp_comm``) enqueues it on ``peer`` (``parallel.p2p.P2PGradReduce``) as in-graph
-    kernels of its comm stream, and :meth:`wait_all` joins that stream instead of waiting on the program."""
+    kernels of its comm stream, and :meth:`wait_all` joins that stream instead of waiting on the program.
+    With ``scatter_parts`` set (``TrainConfig.zero_comm: p2p``) a bucket is reduce-scattered instead."""
 
     def __init__(self, flat: FlatParams, group, dp: int, program, bucket_mb: float = 64.0, tail_mb: float = 16.0,
                  local_names=(), boundaries=None, payload: str = "fp32", active: bool = None,
@@ -73,6 +74,9 @@ class GradBuckets:
         # kernels of its comm stream instead of process-group collectives
         self.transport = transport
         self.peer = peer
+        # zero_comm: p2p -- per bucket the Σg² partial slots of its reduce-scatter (train/optimizer.py
+        # P2PShardedAdamW.parts): the peer (parallel/p2p.py P2PZeroShard) then reduce-scatters instead of all-reducing
+        self.scatter_parts = None
         self._bf16 = {}  # bucket -> (send, recv, reduced shard, gathered) bf16 buffers
         self._cs = None  # GPU: the stream the bf16 exchange chain runs on
         cap = max(1, int(bucket_mb * 1024 * 1024 / 4))
@@ -146,7 +150,11 @@ class GradBuckets:
         g = self.group
         if self.transport == "p2p":
             peer = self.peer
-            peer.on_comm(lambda: peer.bucket_all_reduce_(view))
+            if self.scatter_parts is not None:
+                part = self.scatter_parts[i]
+                peer.on_comm(lambda: peer.bucket_reduce_scatter_(view, part))
+            else:
+                peer.on_comm(lambda: peer.bucket_all_reduce_(view))
         elif self.payload == "bf16":
             self._issue_bf16(i, view)
         else:

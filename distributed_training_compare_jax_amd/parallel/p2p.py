@@ -24,7 +24,8 @@ RCCL call at all: :class:`parallel.tp.TPComm` gathers by summing zero-padded slo
 :class:`P2PPipe` (below) carries the pipeline stages' point-to-point messages over the same kind of buffer
 (``pp_comm: p2p``): sender-staged slots, epoch flags at the receiver, pulled by the receiver.
 :class:`P2PGradReduce` carries a pure-DP step's gradient buckets, loss sum and embedding-gradient gather
-(``dp_comm: p2p``).
+(``dp_comm: p2p``); :class:`P2PZeroShard` the ZeRO-1 step's bucket reduce-scatters and parameter gathers
+(``zero_comm: p2p``).
 """
 
 from __future__ import annotations
@@ -287,8 +288,7 @@ class P2PGradReduce(P2PAllReduce):
             raise ValueError(f"P2P grad reduce: {world} ranks; supports up to 8 (one xGMI hive)")
         self.buckets = [(int(a), int(b)) for a, b in buckets]
         self.payload, self.gather_bytes = payload, int(gather_bytes)
-        half = dp_half_bytes(self.buckets, payload, gather_bytes)
-        self.plan_hash = dp_plan_hash(world, self.buckets, payload, half, gather_bytes)
+        half, self.plan_hash = self._plan(world)
         seen = [None] * world
         dist.all_gather_object(seen, self.plan_hash, group=group)
         for p, h in enumerate(seen):
@@ -306,6 +306,11 @@ class P2PGradReduce(P2PAllReduce):
             use_stream = os.environ.get("DTC_DP_P2P_STREAM", "1") == "1"
         self._cs = torch.cuda.Stream(self.device) if use_stream else None
         self._held = []  # tensors the comm stream still reads (kept alive until join)
+
+    def _plan(self, world: int):
+        """(buffer half in bytes, the hash every rank must share)."""
+        half = dp_half_bytes(self.buckets, self.payload, self.gather_bytes)
+        return half, dp_plan_hash(world, self.buckets, self.payload, half, self.gather_bytes)
 
     def bucket_all_reduce_(self, t: torch.Tensor, bf16: bool = None, max_blocks: int = None) -> torch.Tensor:
         """In-place sum of a slice of the flat fp32 grads over the group (``dtc_dp_allreduce``: pack, barrier,
@@ -352,6 +357,139 @@ class P2PGradReduce(P2PAllReduce):
     def close(self):
         self._held.clear()
         super().close()
+
+
+# ------------------------------------------------------------------------------ ZeRO-1 over the DP buckets
+# ``zero_comm: p2p`` (csrc/p2p.hip, "ZeRO-1 over the DP buckets"): the bucket all-reduce cut in the middle.  Each
+# bucket is reduce-scattered under the backward, the sharded AdamW (train/optimizer.py P2PShardedAdamW) updates the
+# owned slices, and a per-bucket gather moves the updated fp32 parameters and writes the bf16 mirror.
+
+def zero_plan(buckets, world: int, payload: str):
+    """Who owns what under ``zero_comm: p2p``: within a bucket ``[a, b)`` of ``n`` elements rank ``r`` owns the
+    slice ``dp_reduce_kernel`` gives it -- 16-byte pieces of ``e`` = 4 (fp32 payload) or 8 (bf16) elements,
+    ``chunk = ceil(pieces / W)``, pieces ``[min(pieces, r chunk), min(pieces, (r + 1) chunk))``, i.e. elements
+    ``[a + min(n, e lo), a + min(n, e hi))``.  Trailing ranks may own a short or an empty slice; a bucket's slices are
+    disjoint and cover it.
+
+    Returns ``(ranges, offsets)``: ``ranges[r][i] = (lo, hi)`` is rank r's slice of bucket i (``lo == hi`` when
+    empty), ``offsets[r][i]`` its start in the rank's compact m / v shard, and ``offsets[r][len(buckets)]`` the
+    shard's length."""
+    if payload not in ("fp32", "bf16"):
+        raise ValueError(f"zero plan: payload {payload!r}: expected 'fp32' or 'bf16'")
+    if not 1 <= int(world) <= 8:
+        raise ValueError(f"zero plan: {world} ranks; supports 1 to 8")
+    e = 8 if payload == "bf16" else 4
+    ranges, offsets = [], []
+    for r in range(int(world)):
+        rr, oo, cur = [], [], 0
+        for a, b in buckets:
+            a, b = int(a), int(b)
+            n = b - a
+            if n <= 0 or n % 4 or a % 4:
+                raise ValueError(f"zero plan: bucket [{a}, {b}) is not a positive multiple of 4 elements at a "
+                                 "multiple of 4")
+            pieces = -(-n // e)
+            chunk = -(-pieces // world)
+            lo = min(pieces, r * chunk)
+            hi = min(pieces, lo + chunk)
+            rr.append((a + min(n, e * lo), a + min(n, e * hi)))  # (an empty slice: lo == hi == pieces)
+            oo.append(cur)
+            cur += rr[-1][1] - rr[-1][0]
+        oo.append(cur)
+        ranges.append(rr)
+        offsets.append(oo)
+    return ranges, offsets
+
+
+def zero_half_bytes(buckets, world: int, payload: str) -> int:
+    """The buffer half that holds the larger of a bucket's gradient payload and a rank's fp32 parameter slice of
+    that bucket (rank 0's is the largest; at world 1 with the bf16 payload the slice, the whole bucket in fp32, is
+    twice the payload), and the 4-float sums; rounded to 4096."""
+    ranges, _ = zero_plan(buckets, world, payload)
+    need = 16
+    for i, (a, b) in enumerate(buckets):
+        need = max(need, dp_payload_bytes(b - a, payload), 4 * max(rr[i][1] - rr[i][0] for rr in ranges))
+    return (need + 4095) // 4096 * 4096
+
+
+def zero_plan_hash(world: int, buckets, payload: str, half_bytes: int) -> str:
+    """What every rank of the DP group must agree on before it maps a peer, and what a checkpoint's Adam shards
+    were cut by: the bucket list, the world, the payload (it sets the piece size of the ownership) and the half."""
+    import hashlib
+
+    ranges, offsets = zero_plan(buckets, world, payload)
+    plan = ("zero1", int(world), [(int(a), int(b)) for a, b in buckets], str(payload), int(half_bytes), ranges,
+            offsets)
+    return hashlib.sha256(repr(plan).encode()).hexdigest()
+
+
+def dp_rs_slots(numel: int, payload: str, world: int, max_blocks: int) -> int:
+    """Blocks of a bucket's reduce-scatter = its per-block partial slots (csrc/p2p.hip dtc_dp_rs_slots)."""
+    pieces = -(-int(numel) // 8) if payload == "bf16" else int(numel) // 4
+    chunk = -(-pieces // int(world))
+    return min(int(max_blocks), max(1, (chunk + 255) // 256))
+
+
+class P2PZeroShard(P2PGradReduce):
+    """The cross-process calls of a ZeRO-1 step on one peer object (``TrainConfig.zero_comm: p2p``): per bucket a
+    reduce-scatter under the backward (:meth:`bucket_reduce_scatter_`) and, after the sharded update, a parameter
+    gather (:meth:`bucket_param_gather_`); the loss sum and the global sum of squares go through ``all_reduce_`` of
+    a 4-float buffer.  Calls are issued through :meth:`on_comm` like the all-reduce buckets: the one-barrier
+    argument of the kernels needs all of them in one stream order."""
+
+    def __init__(self, group, rank: int, world: int, device, buckets, payload: str = "fp32", max_blocks: int = None,
+                 use_stream: bool = None):
+        super().__init__(group, rank, world, device, buckets, payload, 0, max_blocks, use_stream)
+        self.ranges, self.offsets = zero_plan(self.buckets, world, payload)
+        self.owned = self.ranges[rank]
+
+    def _plan(self, world: int):
+        half = zero_half_bytes(self.buckets, world, self.payload)
+        return half, zero_plan_hash(world, self.buckets, self.payload, half)
+
+    def rs_slots(self, numel: int, bf16: bool = None, max_blocks: int = None) -> int:
+        bf = (self.payload == "bf16") if bf16 is None else bool(bf16)
+        return dp_rs_slots(numel, "bf16" if bf else "fp32", self.world,
+                           self.max_blocks if max_blocks is None else int(max_blocks))
+
+    def bucket_reduce_scatter_(self, t: torch.Tensor, part: torch.Tensor, bf16: bool = None,
+                               max_blocks: int = None) -> torch.Tensor:
+        """``t`` (a bucket of the flat fp32 grads): this rank's slice of it becomes the rank-ordered sum over the
+        group, in place, the rest of ``t`` is left as it is; ``part`` (fp32, :meth:`rs_slots` elements) gets the
+        slice's per-block partial sums of squares."""
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and part.is_cuda
+                and part.dtype == torch.float32 and part.is_contiguous()):
+            raise RuntimeError(f"P2P zero shard: rank {self.rank} bucket is {tuple(t.shape)} {t.dtype} on {t.device}; "
+                               "needs contiguous fp32 GPU tensors")
+        bf = (self.payload == "bf16") if bf16 is None else bool(bf16)
+        N.check(N.lib().dtc_dp_reduce_scatter(t.data_ptr(), t.numel(), int(bf), part.data_ptr(), part.numel(),
+                                              self._bases_ptr, self.rank, self.world, self.half,
+                                              self.epoch.data_ptr(), self.err.data_ptr(),
+                                              self.max_blocks if max_blocks is None else int(max_blocks),
+                                              N.stream_ptr(t.device)), "dtc_dp_reduce_scatter")
+        self.calls += 1
+        return t
+
+    def bucket_param_gather_(self, p: torch.Tensor, mirror=None, n_mirror: int = 0, bf16: bool = None,
+                             max_blocks: int = 1024) -> torch.Tensor:
+        """``p`` (a bucket of the flat fp32 params, this rank's slice of it updated): every other rank's slice is
+        pulled from its owner; ``mirror[:n_mirror]`` (bf16, the bucket's part of the compute mirror) is written
+        from the same values in the same pass.  ``bf16`` selects the ownership plan (that of the gradient
+        payload); the parameters travel as fp32."""
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+            raise RuntimeError(f"P2P zero shard: rank {self.rank} bucket is {tuple(p.shape)} {p.dtype} on {p.device}; "
+                               "needs a contiguous fp32 GPU tensor")
+        if n_mirror and not (mirror is not None and mirror.dtype == torch.bfloat16 and mirror.is_contiguous()
+                             and mirror.numel() >= n_mirror):
+            raise RuntimeError(f"P2P zero shard: rank {self.rank} mirror of {n_mirror} elements needs a contiguous "
+                               "bf16 tensor at least that long")
+        bf = (self.payload == "bf16") if bf16 is None else bool(bf16)
+        N.check(N.lib().dtc_dp_param_gather(p.data_ptr(), N.ptr(mirror) if n_mirror else None, p.numel(),
+                                            int(n_mirror), int(bf), self._bases_ptr, self.rank, self.world, self.half,
+                                            self.epoch.data_ptr(), self.err.data_ptr(), int(max_blocks),
+                                            N.stream_ptr(p.device)), "dtc_dp_param_gather")
+        self.calls += 1
+        return p
 
 
 # ------------------------------------------------------------------------------ pipeline stage messages

@@ -32,7 +32,7 @@ from ..parallel.dp import GradBuckets
 from ..parallel.mesh import Mesh, build_mesh, head_cost_blocks, resolve_degrees, split_layers
 from ..parallel.program import StepProgram, csig
 from ..parallel.tp import TPComm
-from .optimizer import FusedAdamW, ShardedAdamW
+from .optimizer import FusedAdamW, P2PShardedAdamW, ShardedAdamW
 
 
 class Engine:
@@ -57,6 +57,34 @@ class Engine:
                 why = f"tp={tp} (out of scope: the TP and the PP peer buffers have not been run together; use tp = 1)"
             if why:
                 raise ValueError(f"pp_comm: p2p cannot be combined with {why}")
+        # zero_comm: p2p (ZeRO-1 as in-graph kernels on one peer object, parallel/p2p.py P2PZeroShard: per-bucket
+        # reduce-scatters under the backward, the sharded AdamW, per-bucket parameter gathers): refused likewise, before
+        # the dp_comm checks so that both fields set to p2p are answered under this one
+        if train_cfg.zero_comm not in ("rccl", "p2p"):
+            raise ValueError(f"zero_comm={train_cfg.zero_comm!r}: expected 'rccl' or 'p2p'")
+        if train_cfg.zero_comm == "p2p":
+            why = None
+            if train_cfg.zero_stage != 1:
+                why = f"zero_stage={train_cfg.zero_stage} (it names the transport of the sharded optimizer: zero_stage: 1)"
+            elif dinfo.device.type != "cuda":
+                why = "a CPU device (the transport is HIP kernels over IPC-mapped device buffers)"
+            elif tp > 1:
+                why = f"tp={tp} (ZeRO-1 is implemented for pure data parallelism; use tp = 1)"
+            elif pp > 1:
+                why = f"pp={pp} (ZeRO-1 is implemented for pure data parallelism; use pp = 1)"
+            elif train_cfg.dp_comm == "p2p":
+                why = ("dp_comm: p2p (that names the transport of the replicated-optimizer step; under zero_comm: p2p "
+                       "the loss sum rides the ZeRO peer object: leave dp_comm at rccl)")
+            elif dp > 8:
+                why = f"dp={dp} (the peer buffers span one xGMI hive: at most 8 replicas)"
+            elif dp == 1 and not train_cfg.dp_comm_rehearsal:
+                why = "dp == 1 (there is nothing to shard; dp_comm_rehearsal: true runs the transport at world 1)"
+            elif dp == 1 and not (dist.is_available() and dist.is_initialized()):
+                why = "dp == 1 without a process group (the rehearsal needs one for the init handshake)"
+            elif train_cfg.dtype not in ("bf16", "fp32"):
+                why = f"dtype={train_cfg.dtype!r} (bf16 or fp32)"
+            if why:
+                raise ValueError(f"zero_comm: p2p cannot be combined with {why}")
         # dp_comm: p2p (the gradient buckets, the loss sum and the embedding-gradient gather of a pure-DP step as
         # in-graph kernels on one peer object, parallel/p2p.py P2PGradReduce): refused likewise, before any collective
         if train_cfg.dp_comm not in ("rccl", "p2p"):
@@ -70,7 +98,8 @@ class Engine:
             elif pp > 1:
                 why = f"pp={pp} (out of scope: the PP and the DP peer buffers have not been run together; use pp = 1)"
             elif train_cfg.zero_stage == 1:
-                why = "zero_stage=1 (out of scope: ShardedAdamW reduce-scatters through the process group)"
+                why = ("zero_stage=1 (out of scope: ShardedAdamW reduce-scatters through the process group; the "
+                       "in-graph ZeRO-1 is zero_comm: p2p, with dp_comm left at rccl)")
             elif dp > 8:
                 why = f"dp={dp} (the peer buffers span one xGMI hive: at most 8 replicas)"
             elif dp == 1 and not train_cfg.dp_comm_rehearsal:
@@ -246,7 +275,9 @@ class Engine:
             warnings.warn("zero_stage=1 ignored: dp == 1 (nothing to shard); running the replicated AdamW")
         if self.zero and train_cfg.defer_optimizer and dinfo.rank == 0:
             warnings.warn("defer_optimizer ignored under zero_stage=1 (the sharded update ends the step)")
-        if self.zero and train_cfg.dp_grad_dtype == "bf16" and dinfo.rank == 0:
+        # zero_comm: p2p -- the sharded step on the in-graph transport (only with self.zero: checked at the top)
+        self.zero_p2p = bool(self.zero and train_cfg.zero_comm == "p2p")
+        if self.zero and not self.zero_p2p and train_cfg.dp_grad_dtype == "bf16" and dinfo.rank == 0:
             warnings.warn("dp_grad_dtype=bf16 ignored under zero_stage=1: ShardedAdamW reduce-scatters the fp32 grads")
         if self.stage.tp_bf16 and self.stage.wg_group < 0 and dinfo.rank == 0:
             warnings.warn("tp_comm_dtype=bf16 with wgrad_group=-1: the row-parallel "
@@ -263,8 +294,11 @@ class Engine:
                                    tail_mb=train_cfg.dp_tail_mb,
                                    local_names=("wte", "wpe") if self.embed_gather else (), boundaries=bnd,
                                    payload=train_cfg.dp_grad_dtype, active=self.dp_comm,
-                                   transport=train_cfg.dp_comm)
-        if self.zero:
+                                   transport="p2p" if self.zero_p2p else train_cfg.dp_comm)
+        if self.zero_p2p:
+            self.opt = P2PShardedAdamW(self.flat, opt_cfg, self.program, self.buckets.buckets, dp, m.dp_idx,
+                                       train_cfg.dp_grad_dtype)
+        elif self.zero:
             self.opt = ShardedAdamW(self.flat, opt_cfg, self.program, m.dp_group, dp, m.dp_idx)
         else:
             self.opt = FusedAdamW(self.flat, opt_cfg, self.program, tp, m.tp_group, m.pp_group,
@@ -326,6 +360,8 @@ class Engine:
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         if train_cfg.dp_comm == "p2p":
             self._init_dp_p2p()
+        elif self.zero_p2p:
+            self._init_zero_p2p()
         if pp > 1:
             self.recv_x = [torch.zeros(self.mb_rows * T, D, dtype=torch.float32, device=self.device)
                            for _ in range(self.n_micro)]
@@ -446,6 +482,24 @@ class Engine:
         self.dp_p2p = P2PGradReduce(m.dp_group, m.dp_idx, m.dp, self.device, self.buckets.buckets,
                                     self.buckets.payload, gather)
         self.buckets.peer = self.dp_p2p
+        self._loss4 = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self.loss = self._loss4[:1]
+        self._gather_ev = None
+        self.program.before_comm.append(self._join_dp_p2p)
+
+    def _init_zero_p2p(self):
+        """``zero_comm: p2p``: one :class:`parallel.p2p.P2PZeroShard` on the DP group, sized for the larger of a
+        bucket's gradient payload and a rank's fp32 parameter slice of it.  It takes the place of the ``dp_comm:
+        p2p`` peer object (``self.dp_p2p``): the loss sum, the comm stream, the join hook, the health check and
+        :meth:`close` are the same; the buckets issue reduce-scatters into the optimizer's partial slots."""
+        from ..parallel.p2p import P2PZeroShard
+
+        m = self.mesh
+        self.dp_p2p = P2PZeroShard(m.dp_group, m.dp_idx, m.dp, self.device, self.buckets.buckets,
+                                   self.buckets.payload)
+        self.opt.attach(self.dp_p2p)
+        self.buckets.peer = self.dp_p2p
+        self.buckets.scatter_parts = self.opt.parts
         self._loss4 = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.loss = self._loss4[:1]
         self._gather_ev = None
@@ -688,18 +742,19 @@ class Engine:
             # layer's bucket waits for the embedding gather (that collective feeds compute; the bucket
             # only the optimizer).
             first = self.layout.layers[0]
-            if not self.zero and not head_later[0]:  # (ZeRO-1: ShardedAdamW.step reduce-scatters)
+            per_bucket = not self.zero or self.zero_p2p  # (ZeRO-1 over rccl: ShardedAdamW.step reduce-scatters)
+            if per_bucket and not head_later[0]:
                 bk.ready_upto(bk.head_end_offset())
 
             def hook(l):
                 if head_later[0]:
                     head_later[0] = False
-                    if not self.zero:
+                    if per_bucket:
                         bk.ready_upto(bk.head_end_offset())
                 if self.embed_gather and l == first:
                     return
                 bk.ready_upto(bk.layer_end_offset(l))
-        if self.zero:
+        if self.zero and not self.zero_p2p:
             hook = None  # grads are reduce-scattered in one call by ShardedAdamW.step
         dx_hook = None
         if self.embed_gather:
@@ -728,7 +783,14 @@ class Engine:
             opt.chunk_ready(len(opt.chunks) - 1, side)  # local wte/wpe grads: overlaps the tail bucket
         else:
             st.embed_backward(ctx, dx, step, 0.0)
-        if not self.zero:
+        if self.zero_p2p:
+            # every bucket's reduce-scatter and the loss sum joined; P2PShardedAdamW.step pads the step's calls
+            # to an even count after its parameter gathers
+            if opt.reducer is not None:
+                opt.reducer.flush_all()  # grads must be final (launches nothing when every window was flushed)
+            bk.ready_all()
+            bk.wait_all()
+        elif not self.zero:
             bk.ready_all()
             if self.dp_p2p is not None:
                 # an even number of calls per step (every replay starts on the same buffer half); a barrier

@@ -229,6 +229,90 @@ class FusedAdamW:
         return float(self.sumsq.item()) ** 0.5
 
 
+class P2PShardedAdamW:
+    """ZeRO-1 over the DP buckets as in-graph peer-to-peer kernels (``TrainConfig.zero_comm: p2p``).
+
+    The ownership is the bucket reduction's own (``parallel.p2p.zero_plan``): within each gradient bucket rank r
+    owns the slice the P2P reduce gives it, so the reduce-scatters go out bucket by bucket under the backward (the
+    engine's hooks, through ``GradBuckets``), each leaving its slice's Σg² as per-block partials.  :meth:`step`:
+
+    1. ``sum_finish`` over all buckets' partial slots, in slot order: this rank's Σg²; the peer object's
+       rank-ordered one-shot sum of a 4-float buffer makes it the global one, the same bits on every rank (the
+       replicated optimizer's norm up to summation order);
+    2. the AdamW kernel (``adamw_flat``) on each owned range with the compact m / v.  It does NOT write the bf16
+       mirror: the gather writes the whole mirror, the owned ranges included, in its one pass;
+    3. per bucket, the parameter gather (fp32 params + bf16 mirror), then the transposed / FP8 / MXFP8 mirrors as
+       ``FlatParams.refresh_mirror`` rebuilds them after its cast.
+
+    ``flat.exp_avg`` / ``exp_avg_sq`` are replaced by the compact shard (8 · owned bytes), so checkpoints hold each
+    rank's shard (resume under the same plan: ``plan_hash``)."""
+
+    def __init__(self, flat: FlatParams, cfg: OptimConfig, program, buckets, dp: int, dp_idx: int, payload: str):
+        from ..parallel.p2p import zero_plan
+
+        self.flat, self.cfg, self.program = flat, cfg, program
+        self.dp, self.rank, self.payload = dp, dp_idx, payload
+        self.buckets = [(int(a), int(b)) for a, b in buckets]
+        if not self.buckets or self.buckets[0][0] != 0 or self.buckets[-1][1] != flat.numel or any(
+                a[1] != b[0] for a, b in zip(self.buckets, self.buckets[1:])):
+            raise ValueError("zero_comm: p2p needs gradient buckets that tile the whole flat buffer "
+                             "(dp_embed_gather stays off under ZeRO-1)")
+        ranges, offsets = zero_plan(self.buckets, dp, payload)
+        self.owned, self.offsets = ranges[dp_idx], offsets[dp_idx]
+        self.n_owned = self.offsets[-1]
+        dev = flat.device
+        flat.exp_avg = torch.zeros(max(self.n_owned, 4), dtype=torch.float32, device=dev)[:self.n_owned]
+        flat.exp_avg_sq = torch.zeros(max(self.n_owned, 4), dtype=torch.float32, device=dev)[:self.n_owned]
+        self._sq4 = torch.zeros(4, dtype=torch.float32, device=dev)  # the sum moves 16-byte pieces
+        self.sumsq = self._sq4[:1]
+        self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.reducer = None
+        self.peer = None
+        self.plan_hash = None
+        self.part, self.parts = None, []
+
+    def attach(self, peer):
+        """The peer object (``parallel.p2p.P2PZeroShard``, created once the engine's buffers exist) and, sized by
+        its grid cap, the partial slots of every bucket's reduce-scatter."""
+        assert peer.buckets == self.buckets and peer.owned == self.owned
+        self.peer, self.plan_hash = peer, peer.plan_hash
+        slots = [peer.rs_slots(b - a) for a, b in self.buckets]
+        self.part = torch.zeros(sum(slots), dtype=torch.float32, device=self.flat.device)
+        self.parts, off = [], 0
+        for k in slots:
+            self.parts.append(self.part[off:off + k])
+            off += k
+
+    def step(self):
+        """After every bucket's reduce-scatter has been joined to the current stream."""
+        f, c, peer = self.flat, self.cfg, self.peer
+        O.sum_finish(self.part, self.sumsq, step=self.step_t)
+        peer.on_comm(lambda: peer.all_reduce_(self._sq4))
+        peer.join()
+        for (lo, hi), off in zip(self.owned, self.offsets):
+            if hi > lo:
+                O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[off:off + hi - lo],
+                             f.exp_avg_sq[off:off + hi - lo], None, 0, self.step_t, self.sumsq, c.lr, c.b1, c.b2,
+                             c.eps, c.weight_decay, c.grad_clip)
+        nm = f.n_mirror if f.use_mirror else 0
+
+        def gathers():
+            for a, b in self.buckets:
+                k = min(max(nm - a, 0), b - a)
+                peer.bucket_param_gather_(f.params[a:b], f.mirror[a:] if k else None, k)
+            peer.end_step()  # an even number of calls per step: every replay starts on the same buffer half
+
+        peer.on_comm(gathers)
+        peer.join()
+        if nm > 0:
+            f.refresh_transposed()
+        f.refresh_fp8()
+        f.refresh_mxfp8()
+
+    def grad_norm(self) -> float:
+        return float(self.sumsq.item()) ** 0.5
+
+
 class ShardedAdamW:
     """ZeRO-1 over the data-parallel group: each DP rank owns 1/dp of the Adam state.
 

@@ -41,11 +41,22 @@ def save(eng, output_dir: str, step: int):
     lr = getattr(eng, "layout", None)
     meta = dict(step=step, dp=m.dp, tp=m.tp, pp=m.pp, rank=m.rank, dp_idx=m.dp_idx, tp_idx=m.tp_idx,
                 pp_idx=m.pp_idx, slots=slots, model=eng.mcfg.name,
-                zero_stage=int(getattr(eng, "zero", False)),
+                zero_stage=int(getattr(eng, "zero", False)), **_zero_meta(eng),
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
                 vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab))
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
         json.dump(meta, fh)
+
+
+def _zero_meta(eng) -> dict:
+    """What a ZeRO-1 Adam shard was cut by: the transport (``rccl``: equal contiguous shares; ``p2p``: the bucket
+    reduction's slices) and, for ``p2p``, the bucket list, the payload and the plan hash."""
+    if not getattr(eng, "zero", False):
+        return {}
+    if not getattr(eng, "zero_p2p", False):
+        return dict(zero_comm="rccl")
+    return dict(zero_comm="p2p", zero_plan=eng.opt.plan_hash, zero_buckets=[list(b) for b in eng.opt.buckets],
+                zero_payload=eng.opt.payload)
 
 
 def _read_metas(d: str) -> Dict[int, dict]:
@@ -84,6 +95,23 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
     if zero_now and m0["dp"] != mesh.dp:
         raise ValueError(f"zero_stage=1 checkpoint was written at dp={m0['dp']}, this run has dp={mesh.dp}: "
                          "each rank's Adam shard resumes only at the same dp")
+    if zero_now:
+        now = _zero_meta(eng)
+        ck = dict(zero_comm=m0.get("zero_comm", "rccl"), zero_buckets=m0.get("zero_buckets"),
+                  zero_payload=m0.get("zero_payload"), zero_plan=m0.get("zero_plan"))
+        if ck["zero_comm"] != now["zero_comm"]:
+            raise ValueError(f"checkpoint zero_comm={ck['zero_comm']} but this run has zero_comm={now['zero_comm']}: "
+                             "the two cut the Adam state differently (resume with the transport that wrote it)")
+        if now["zero_comm"] == "p2p":
+            if ck["zero_payload"] != now["zero_payload"]:
+                raise ValueError(f"zero_comm: p2p checkpoint was written with dp_grad_dtype={ck['zero_payload']}, this "
+                                 f"run has dp_grad_dtype={now['zero_payload']}: the payload sets each rank's slices")
+            if ck["zero_buckets"] != now["zero_buckets"]:
+                raise ValueError("zero_comm: p2p checkpoint was written with other gradient buckets (dp_bucket_mb / "
+                                 "dp_tail_mb differ): each rank's Adam shard follows the bucket edges")
+            if ck["zero_plan"] != now["zero_plan"]:
+                raise ValueError(f"zero_comm: p2p checkpoint plan {str(ck['zero_plan'])[:12]} differs from this run's "
+                                 f"{str(now['zero_plan'])[:12]} (zero_plan): the ownership plan changed")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
     for r, m in metas.items():
@@ -159,6 +187,7 @@ def load_into(eng, output_dir: str, step: int):
     f.exp_avg.copy_(st["exp_avg"].to(f.device))
     f.exp_avg_sq.copy_(st["exp_avg_sq"].to(f.device))
     eng.opt.step_t.copy_(st["step_t"].to(f.device))
+    # (under ZeRO-1 every rank's params file holds the full, gathered parameters)
     f.refresh_mirror()
     return int(st["step"])
 
