@@ -51,6 +51,14 @@ are optional and default to the reference behaviour:
   per-bucket parameter gather that also writes the bf16 mirror, all in-graph peer-to-peer kernels,
   ``parallel/p2p.py P2PZeroShard`` + ``train/optimizer.py P2PShardedAdamW``: one hipGraph per step, ``dp_grad_dtype``
   honoured; GPU, 2 <= dp <= 8 or the dp = 1 rehearsal, tp = pp = 1, ``dp_comm: rccl``; default ``rccl``).
+* ``TrainConfig.grad_accum`` (k, default 1): ``batch`` stays the global batch of ONE optimizer update; each rank's
+  local rows run as k microbatches of ``b_local / k`` rows inside one step (one update, one loss, one CSV row), the
+  gradients accumulated in place, so the peak activation memory is that of one microbatch.  Every DP / TP / ZeRO-1
+  layout and transport (``train/engine.py``); pp > 1 accumulates through ``pp_microbatches`` instead.
+* ``OptimConfig.lr_schedule`` (``constant`` | ``warmup_cosine``) with ``lr_warmup_steps`` (W), ``lr_decay_steps``
+  (N, warmup included) and ``lr_min_ratio`` (r): ``optax.warmup_cosine_decay_schedule(0, lr, W, N, lr * r)`` under
+  ``scale_by_schedule``, evaluated on the device once per step from the step counter (``csrc/elementwise.hip``), so
+  a captured step replays the schedule instead of one frozen rate; :meth:`OptimConfig.lr_at` is its float64 value.
 """
 
 from __future__ import annotations
@@ -115,6 +123,47 @@ class OptimConfig:
     b1: float = 0.9
     b2: float = 0.999
     eps: float = 1e-8
+    # --- extensions (defaults = reference behaviour: one constant rate) ---
+    lr_schedule: str = "constant"  # constant | warmup_cosine
+    lr_warmup_steps: int = 0       # W: linear warmup from 0 over the first W updates
+    lr_decay_steps: int = 0        # N: the cosine reaches lr * lr_min_ratio at update N (warmup included)
+    lr_min_ratio: float = 0.0      # r: the floor as a fraction of lr
+
+    def __post_init__(self):
+        if self.lr_schedule not in ("constant", "warmup_cosine"):
+            raise ValueError(f"lr_schedule={self.lr_schedule!r}: expected 'constant' or 'warmup_cosine'")
+        W, N, r = self.lr_warmup_steps, self.lr_decay_steps, self.lr_min_ratio
+        if isinstance(W, bool) or isinstance(N, bool) or int(W) != W or int(N) != N or W < 0 or N < 0:
+            raise ValueError(f"lr_warmup_steps={W!r}, lr_decay_steps={N!r}: expected non-negative integers")
+        if not (0.0 <= float(r) <= 1.0):
+            raise ValueError(f"lr_min_ratio={r!r}: expected a ratio in [0, 1]")
+        if self.lr_schedule == "warmup_cosine" and N <= W:
+            raise ValueError(f"lr_schedule=warmup_cosine needs lr_decay_steps > lr_warmup_steps (got N={N}, W={W}: "
+                             "N counts the warmup)")
+
+    @property
+    def scheduled(self) -> bool:
+        return self.lr_schedule != "constant"
+
+    def lr_at(self, t: int) -> float:
+        """The learning rate of update ``t`` (1-based: the already-incremented step counter) in float64.  optax
+        counts the updates already applied, c = t - 1: lr * c / W during warmup, then the cosine from lr down to
+        lr * r over the N - W steps that follow, then lr * r."""
+        import math
+
+        if not self.scheduled:
+            return float(self.lr)
+        W, N, r = int(self.lr_warmup_steps), int(self.lr_decay_steps), float(self.lr_min_ratio)
+        c = int(t) - 1
+        if c < W:
+            return float(self.lr) * c / W
+        x = min(c - W, N - W) / (N - W)
+        return float(self.lr) * (r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * x)))
+
+    def schedule_key(self) -> str:
+        """What a checkpoint records so that a resume under other schedule fields is refused."""
+        return (f"{self.lr_schedule}:{int(self.lr_warmup_steps)}:{int(self.lr_decay_steps)}:"
+                f"{float(self.lr_min_ratio)!r}")
 
 
 @dataclass(frozen=True)
@@ -131,6 +180,9 @@ class TrainConfig:
     # pipeline parallelism
     pp_microbatches: int = 1
     # --- extensions ---
+    # gradient accumulation (pp == 1): each rank's local batch as grad_accum microbatches inside one step; `batch`
+    # stays the global batch of one optimizer update (train/engine.py)
+    grad_accum: int = 1
     dtype: str = "bf16"
     # bf16 | fp8 | mxfp8: the forward qkv / out_proj / fc1 / fc2 GEMMs.  fp8 = e4m3 operands with per-tensor
     # power-of-two scales from the current tensor (ops/fp8.py); mxfp8 = e4m3 operands with one power-of-two scale per

@@ -482,7 +482,26 @@ __global__ void __launch_bounds__(256) sumsq_stage1(const float* __restrict__ x,
   if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void sumsq_stage2(const float* __restrict__ part, int P, float* __restrict__ out, int64_t* __restrict__ step) {
+// Learning-rate schedule evaluated on the device (OptimConfig.lr_schedule): the thread that finishes the norm and
+// bumps the step counter also writes this update's rate into `out`, once per step, so a captured step replays the
+// schedule from the counter instead of a rate frozen into a kernel argument.  optax's warmup_cosine_decay_schedule
+// (0 -> lr over `warmup` updates, a cosine down to lr * min_ratio at update `decay`, constant after) under
+// scale_by_schedule: the count is the number of updates already applied, t - 1 with the bumped counter t.
+struct LrSched {
+  float* out;      // null: no schedule (the AdamW kernels use their by-value lr)
+  float lr, min_ratio;
+  long warmup, decay;  // decay > warmup (host-checked)
+};
+__device__ __forceinline__ float lr_schedule_at(const LrSched& s, int64_t t) {
+  const long c = (long)t - 1;
+  if (c < s.warmup) return s.lr * ((float)c / (float)s.warmup);
+  const long span = s.decay - s.warmup, k = c - s.warmup < span ? c - s.warmup : span;
+  const float x = (float)k / (float)span;
+  return s.lr * (s.min_ratio + (1.f - s.min_ratio) * (0.5f * (1.f + cospif(x))));
+}
+
+__global__ void sumsq_stage2(const float* __restrict__ part, int P, float* __restrict__ out, int64_t* __restrict__ step,
+                             LrSched sched) {
   __shared__ double red[16];
   // 8 independent loads in flight per thread (~16-20k partials: the one-load-per-iteration chain took
   // 10.5 us, on the critical path before the AdamW launch); fixed order: deterministic
@@ -506,6 +525,7 @@ __global__ void sumsq_stage2(const float* __restrict__ part, int P, float* __res
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
     out[0] = (float)t;
     if (step) step[0] += 1;
+    if (sched.out && step) sched.out[0] = lr_schedule_at(sched, step[0]);
   }
 }
 
@@ -520,7 +540,8 @@ template <bool STRIDE, int CH>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, bf16* __restrict__ mirror, long n, long n_mirror,
                              const int64_t* __restrict__ step, const float* __restrict__ sumsq, float lr, float b1,
-                             float b2, float eps, float wd, float max_norm, const float* __restrict__ enable) {
+                             float b2, float eps, float wd, float max_norm, const float* __restrict__ enable,
+                             const float* __restrict__ lr_dev) {
   // CH 4-element groups per thread, 1024 elements apart (the per-thread clip / bias-correction
   // prologue — a sqrt, two powf and a division — amortised over 4*CH elements)
   long i = (long)blockIdx.x * blockDim.x * 4 * CH + threadIdx.x * 4;
@@ -530,6 +551,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   const float clip = (max_norm > 0.f && !(norm < max_norm)) ? max_norm / norm : 1.f;
   const float t = (float)step[0];
   const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
+  if (lr_dev) lr = lr_dev[0];  // this update's scheduled rate (null: the by-value constant)
   const long stride = STRIDE ? (long)gridDim.x * blockDim.x * 4 * CH : n;
   do {
     if (STRIDE && i >= n) break;
@@ -591,8 +613,10 @@ struct AwHyper {
   const int64_t* step;
   const float* sumsq;
   float lr, b1, b2, eps, wd, max_norm;
+  const float* lr_dev;  // this update's scheduled rate, or null: the by-value lr
 };
-__device__ __forceinline__ void aw_prologue(const AwHyper& h, float& clip, float& bc1, float& bc2) {
+__device__ __forceinline__ void aw_prologue(const AwHyper& h, float& clip, float& bc1, float& bc2, float& lr) {
+  lr = h.lr_dev ? h.lr_dev[0] : h.lr;
   const float norm = sqrtf(h.sumsq[0]);
   clip = (h.max_norm > 0.f && !(norm < h.max_norm)) ? h.max_norm / norm : 1.f;
   const float t = (float)h.step[0];
@@ -620,8 +644,8 @@ __global__ void __launch_bounds__(256) adamw_seg_kernel(float* __restrict__ p, c
     if ((int)blockIdx.x >= segs.s[mid].blk0) lo = mid; else hi = mid - 1;
   }
   const AwSeg& S = segs.s[lo];
-  float clip, bc1, bc2;
-  aw_prologue(h, clip, bc1, bc2);
+  float clip, bc1, bc2, lr;
+  aw_prologue(h, clip, bc1, bc2, lr);
   const long base = S.lo + (long)(blockIdx.x - S.blk0) * 256 * 16;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -630,7 +654,7 @@ __global__ void __launch_bounds__(256) adamw_seg_kernel(float* __restrict__ p, c
     DTC_ASSERT(j + 4 <= S.lo + S.n);
     f32x4 pp = __builtin_nontemporal_load((f32x4*)(p + j)), gg = __builtin_nontemporal_load((const f32x4*)(g + j));
     f32x4 mm = __builtin_nontemporal_load((f32x4*)(m + j)), vv = __builtin_nontemporal_load((f32x4*)(v + j));
-    adamw4(pp, gg, mm, vv, clip, bc1, bc2, h.lr, h.b1, h.b2, h.eps, h.wd);
+    adamw4(pp, gg, mm, vv, clip, bc1, bc2, lr, h.b1, h.b2, h.eps, h.wd);
     __builtin_nontemporal_store(pp, (f32x4*)(p + j));
     __builtin_nontemporal_store(mm, (f32x4*)(m + j));
     __builtin_nontemporal_store(vv, (f32x4*)(v + j));
@@ -662,8 +686,8 @@ __global__ void __launch_bounds__(256) adamw_tr_kernel(float* __restrict__ p, co
   DTC_ASSERT(bi >= 0 && bi < ((T.rows + 63) / 64) * tcols && T.cols % 4 == 0 && T.rows % 8 == 0);
   const int r0 = (bi / tcols) * 64, c0 = (bi % tcols) * 64;
   __shared__ bf16 tile[64][64 + 1];  // row length 65: the column reads below spread over the banks
-  float clip, bc1, bc2;
-  aw_prologue(h, clip, bc1, bc2);
+  float clip, bc1, bc2, lr;
+  aw_prologue(h, clip, bc1, bc2, lr);
   const int tid = threadIdx.x;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {  // 64 rows x 16 groups of 4 columns: a row is 16 lanes x 16 B
@@ -673,7 +697,7 @@ __global__ void __launch_bounds__(256) adamw_tr_kernel(float* __restrict__ p, co
       const long j = T.off + (long)(r0 + r) * T.cols + c0 + c4;
       f32x4 pp = __builtin_nontemporal_load((f32x4*)(p + j)), gg = __builtin_nontemporal_load((const f32x4*)(g + j));
       f32x4 mm = __builtin_nontemporal_load((f32x4*)(m + j)), vv = __builtin_nontemporal_load((f32x4*)(v + j));
-      adamw4(pp, gg, mm, vv, clip, bc1, bc2, h.lr, h.b1, h.b2, h.eps, h.wd);
+      adamw4(pp, gg, mm, vv, clip, bc1, bc2, lr, h.b1, h.b2, h.eps, h.wd);
       __builtin_nontemporal_store(pp, (f32x4*)(p + j));
       __builtin_nontemporal_store(mm, (f32x4*)(m + j));
       __builtin_nontemporal_store(vv, (f32x4*)(v + j));
@@ -893,14 +917,29 @@ int dtc_ce_bwd_f32(float* logits, long ld, const float* lse, const int* labels, 
 
 long dtc_sumsq_workspace_bytes() { return SS_BLOCKS * 4; }
 
-int dtc_sumsq_segments(const float* x, const double* seg, int S, float* out, int64_t* step, float* ws, long ws_bytes,
-                       hipStream_t st) {
+// `lr_out` non-null: the finishing thread also writes the scheduled rate of the bumped step (LrSched)
+static int lr_sched_make(LrSched& s, float* lr_out, float lr, float min_ratio, long warmup, long decay,
+                         const int64_t* step) {
+  s = LrSched{lr_out, lr, min_ratio, warmup, decay};
+  if (lr_out && (!step || warmup < 0 || decay <= warmup || !(min_ratio >= 0.f && min_ratio <= 1.f))) return 3012;
+  return 0;
+}
+
+int dtc_sumsq_segments_lr(const float* x, const double* seg, int S, float* out, int64_t* step, float* ws, long ws_bytes,
+                          float* lr_out, float lr, float min_ratio, long warmup, long decay, hipStream_t st) {
   if (ws_bytes < SS_BLOCKS * 4) return 3004;
+  LrSched sched;
+  if (int rc = lr_sched_make(sched, lr_out, lr, min_ratio, warmup, decay, step)) return rc;
   hipLaunchKernelGGL(sumsq_stage1, dim3(SS_BLOCKS), dim3(256), 0, st, x, seg, S, ws);
   DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(1024), 0, st, ws, SS_BLOCKS, out, step);
+  hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(1024), 0, st, ws, SS_BLOCKS, out, step, sched);
   DTC_CHECK_LAUNCH();
   return 0;
+}
+
+int dtc_sumsq_segments(const float* x, const double* seg, int S, float* out, int64_t* step, float* ws, long ws_bytes,
+                       hipStream_t st) {
+  return dtc_sumsq_segments_lr(x, seg, S, out, step, ws, ws_bytes, nullptr, 0.f, 0.f, 0, 0, st);
 }
 
 // Incremental global norm: chunk i of the grads is reduced into part[0:nblocks] as soon as it
@@ -912,8 +951,30 @@ int dtc_sumsq_partial(const float* x, const double* seg, int S, float* part, int
   return 0;
 }
 
+int dtc_sum_finish_lr(const float* part, int P, float* out, int64_t* step, float* lr_out, float lr, float min_ratio,
+                      long warmup, long decay, hipStream_t st) {
+  LrSched sched;
+  if (int rc = lr_sched_make(sched, lr_out, lr, min_ratio, warmup, decay, step)) return rc;
+  hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(1024), 0, st, part, P, out, step, sched);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
 int dtc_sum_finish(const float* part, int P, float* out, int64_t* step, hipStream_t st) {
-  hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(1024), 0, st, part, P, out, step);
+  return dtc_sum_finish_lr(part, P, out, step, nullptr, 0.f, 0.f, 0, 0, st);
+}
+
+// `lr_dev` (fp32 [1], written by the norm's finishing thread) replaces the by-value lr when non-null
+int dtc_adamw_lr(float* p, const float* g, float* m, float* v, bf16* mirror, long n, long n_mirror, const int64_t* step,
+                 const float* sumsq, float lr, float b1, float b2, float eps, float wd, float max_norm,
+                 const float* enable, int max_blocks, const float* lr_dev, hipStream_t st) {
+  if (n % 4 || n_mirror % 4) return 3005;
+  const long blocks = blocks_for(n / 4, 256 * DTC_ADAMW_CH);
+  if (max_blocks > 0 && blocks > max_blocks)  // capped grid, grid-stride over the rest
+    hipLaunchKernelGGL((adamw_kernel<true, DTC_ADAMW_CH>), dim3(max_blocks), dim3(256), 0, st, p, g, m, v, mirror, n, n_mirror,
+                       step, sumsq, lr, b1, b2, eps, wd, max_norm, enable, lr_dev);
+  else  // DTC_ADAMW_CH 4-element groups per thread, one grid step
+    hipLaunchKernelGGL((adamw_kernel<false, DTC_ADAMW_CH>), dim3(blocks), dim3(256), 0, st, p, g, m, v, mirror, n, n_mirror, step, sumsq, lr, b1, b2, eps, wd, max_norm, enable, lr_dev);
   DTC_CHECK_LAUNCH();
   return 0;
 }
@@ -921,15 +982,8 @@ int dtc_sum_finish(const float* part, int P, float* out, int64_t* step, hipStrea
 int dtc_adamw(float* p, const float* g, float* m, float* v, bf16* mirror, long n, long n_mirror, const int64_t* step,
               const float* sumsq, float lr, float b1, float b2, float eps, float wd, float max_norm,
               const float* enable, int max_blocks, hipStream_t st) {
-  if (n % 4 || n_mirror % 4) return 3005;
-  const long blocks = blocks_for(n / 4, 256 * DTC_ADAMW_CH);
-  if (max_blocks > 0 && blocks > max_blocks)  // capped grid, grid-stride over the rest
-    hipLaunchKernelGGL((adamw_kernel<true, DTC_ADAMW_CH>), dim3(max_blocks), dim3(256), 0, st, p, g, m, v, mirror, n, n_mirror,
-                       step, sumsq, lr, b1, b2, eps, wd, max_norm, enable);
-  else  // DTC_ADAMW_CH 4-element groups per thread, one grid step
-    hipLaunchKernelGGL((adamw_kernel<false, DTC_ADAMW_CH>), dim3(blocks), dim3(256), 0, st, p, g, m, v, mirror, n, n_mirror, step, sumsq, lr, b1, b2, eps, wd, max_norm, enable);
-  DTC_CHECK_LAUNCH();
-  return 0;
+  return dtc_adamw_lr(p, g, m, v, mirror, n, n_mirror, step, sumsq, lr, b1, b2, eps, wd, max_norm, enable, max_blocks,
+                      nullptr, st);
 }
 
 // fused AdamW + transposed mirror: segments (element-wise) and tiles (with W^T); the host builds both lists
@@ -937,15 +991,15 @@ int dtc_aw_max_seg() { return AW_MAX_SEG; }
 int dtc_aw_max_tasks() { return AWT_MAX; }
 int dtc_aw_seg_bytes() { return (int)sizeof(AwSeg); }
 int dtc_aw_task_bytes() { return (int)sizeof(AwtTask); }
-int dtc_adamw_tr(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,
-                 const AwtBatch* tasks, const int64_t* step, const float* sumsq, float lr, float b1, float b2, float eps,
-                 float wd, float max_norm, hipStream_t st) {
+int dtc_adamw_tr_lr(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,
+                    const AwtBatch* tasks, const int64_t* step, const float* sumsq, float lr, float b1, float b2,
+                    float eps, float wd, float max_norm, const float* lr_dev, hipStream_t st) {
   if (segs->nseg > AW_MAX_SEG || tasks->ntasks > AWT_MAX || n_mirror % 4) return 3005;
   for (int i = 0; i < segs->nseg; ++i)
     if (segs->s[i].lo % 4 || segs->s[i].n % 4) return 3005;
   for (int i = 0; i < tasks->ntasks; ++i)
     if (tasks->t[i].rows % 8 || tasks->t[i].cols % 4 || tasks->t[i].off % 4) return 3011;
-  const AwHyper h{step, sumsq, lr, b1, b2, eps, wd, max_norm};
+  const AwHyper h{step, sumsq, lr, b1, b2, eps, wd, max_norm, lr_dev};
   if (segs->nseg > 0 && segs->nblocks > 0) {
     hipLaunchKernelGGL(adamw_seg_kernel, dim3(segs->nblocks), dim3(256), 0, st, p, g, m, v, mirror, n_mirror, *segs, h);
     DTC_CHECK_LAUNCH();
@@ -955,6 +1009,13 @@ int dtc_adamw_tr(float* p, const float* g, float* m, float* v, bf16* mirror, lon
     DTC_CHECK_LAUNCH();
   }
   return 0;
+}
+
+int dtc_adamw_tr(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,
+                 const AwtBatch* tasks, const int64_t* step, const float* sumsq, float lr, float b1, float b2, float eps,
+                 float wd, float max_norm, hipStream_t st) {
+  return dtc_adamw_tr_lr(p, g, m, v, mirror, n_mirror, segs, tasks, step, sumsq, lr, b1, b2, eps, wd, max_norm, nullptr,
+                         st);
 }
 
 int dtc_tr_max_tasks() { return TR_MAX_TASKS; }

@@ -172,6 +172,9 @@ class GPTStage:
         # sequence parallelism (enable_sequence_parallel): residual stream / LayerNorms / embedding output on
         # rows/tp rows per rank; the LN and row-parallel-bias grads are then per-rank partials (_sp_sum)
         self.sp = False
+        # set by the engine around a backward whose gradients are still partial sums over microbatches
+        # (grad_accum): the TP sum of the per-rank partial grads waits for the last one (_sp_sum)
+        self.sp_hold = False
         self._sp_idx: Dict = {}
         # FP8 forward (enable_fp8_forward): qkv / out_proj / fc1 / fc2 forwards on e4m3 operands
         self.fp8 = False
@@ -283,7 +286,7 @@ class GPTStage:
     def _sp_sum(self, keys):
         """Sum the partial grads of layers / "head" ``keys`` over the TP group: one gather, one all-reduce
         (in-graph on the P2P path), one scatter back."""
-        if not self.sp or not keys:
+        if not self.sp or not keys or self.sp_hold:
             return
         k = tuple(keys)
         idx = self._sp_idx.get(k)

@@ -173,6 +173,10 @@ def _declare(lib):
         "dtc_sumsq_workspace_bytes": ([], l),
         "dtc_sumsq_partial": ([vp, vp, i, vp, i, vp], i),
         "dtc_sum_finish": ([vp, i, vp, vp, vp], i),
+        "dtc_sumsq_segments_lr": ([vp, vp, i, vp, vp, vp, l, vp, f, f, l, l, vp], i),
+        "dtc_sum_finish_lr": ([vp, i, vp, vp, vp, f, f, l, l, vp], i),
+        "dtc_adamw_lr": ([vp, vp, vp, vp, vp, l, l, vp, vp, f, f, f, f, f, f, vp, i, vp, vp], i),
+        "dtc_adamw_tr_lr": ([vp, vp, vp, vp, vp, l, vp, vp, vp, vp, f, f, f, f, f, f, vp, vp], i),
         "dtc_adamw": ([vp, vp, vp, vp, vp, l, l, vp, vp, f, f, f, f, f, f, vp, i, vp], i),
         "dtc_cast_f32_bf16": ([vp, vp, l, vp], i),
         "dtc_transpose_batch": ([vp, vp], i),

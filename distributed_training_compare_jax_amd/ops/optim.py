@@ -34,9 +34,42 @@ def make_segments(segments, device) -> torch.Tensor:
     return t.to(device)
 
 
+class LrSchedule:
+    """A learning-rate schedule evaluated on the device (``OptimConfig.lr_schedule: warmup_cosine``).
+
+    ``out`` (fp32 [1]) holds the rate of the current update: the kernel that finishes the global norm and bumps the
+    step counter (:func:`sum_finish` / :func:`sumsq_segments` with ``sched=``) writes it, the AdamW kernels read it
+    through ``lr_dev=`` instead of their by-value ``lr``.  A captured step therefore replays the schedule, as it
+    already replays the bias correction, from the device step counter.  On CPU tensors the same functions write
+    ``cfg.lr_at(t)`` rounded to fp32."""
+
+    def __init__(self, cfg, device):
+        assert cfg.scheduled
+        self.cfg = cfg
+        self.lr, self.min_ratio = float(cfg.lr), float(cfg.lr_min_ratio)
+        self.warmup, self.decay = int(cfg.lr_warmup_steps), int(cfg.lr_decay_steps)
+        self.out = torch.zeros(1, dtype=torch.float32, device=device)
+
+    @classmethod
+    def of(cls, cfg, device) -> "Optional[LrSchedule]":
+        return cls(cfg, device) if getattr(cfg, "scheduled", False) else None
+
+    def _write_cpu(self, step: torch.Tensor):
+        self.out.fill_(self.cfg.lr_at(int(step[0])))
+
+    def _args(self):
+        return self.out.data_ptr(), self.lr, self.min_ratio, self.warmup, self.decay
+
+
+def _lr_dev(sched: "Optional[LrSchedule]"):
+    return None if sched is None else sched.out
+
+
 def sumsq_segments(flat: torch.Tensor, segments: torch.Tensor, out: torch.Tensor,
-                   step: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[0] = Σ_s w_s·Σ_{i∈s} flat[i]²  (fp32).  If ``step`` is given it is incremented by 1."""
+                   step: Optional[torch.Tensor] = None, sched: Optional[LrSchedule] = None) -> torch.Tensor:
+    """out[0] = Σ_s w_s·Σ_{i∈s} flat[i]²  (fp32).  If ``step`` is given it is incremented by 1, and with ``sched``
+    the rate of that update is written to ``sched.out``."""
+    assert sched is None or step is not None, "a schedule is evaluated where the step counter is bumped"
     if not flat.is_cuda:
         acc = torch.zeros((), dtype=torch.float64)
         for o, n, w in segments.tolist():
@@ -45,9 +78,16 @@ def sumsq_segments(flat: torch.Tensor, segments: torch.Tensor, out: torch.Tensor
         out.fill_(float(acc))
         if step is not None:
             step.add_(1)
+        if sched is not None:
+            sched._write_cpu(step)
         return out
     L = N.lib()
     ws = _workspace(flat.device, int(L.dtc_sumsq_workspace_bytes()))
+    if sched is not None:
+        N.check(L.dtc_sumsq_segments_lr(flat.data_ptr(), segments.data_ptr(), segments.shape[0], out.data_ptr(),
+                                        N.ptr(step), ws.data_ptr(), ws.numel(), *sched._args(),
+                                        N.stream_ptr(flat.device)), "dtc_sumsq_segments_lr")
+        return out
     N.check(L.dtc_sumsq_segments(flat.data_ptr(), segments.data_ptr(), segments.shape[0], out.data_ptr(),
                                  N.ptr(step), ws.data_ptr(), ws.numel(), N.stream_ptr(flat.device)),
             "dtc_sumsq_segments")
@@ -69,12 +109,21 @@ def sumsq_partial(flat: torch.Tensor, segments: torch.Tensor, part: torch.Tensor
     return part
 
 
-def sum_finish(part: torch.Tensor, out: torch.Tensor, step: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[0] = Σ part (fixed order, fp64 accumulate); bumps ``step`` if given."""
+def sum_finish(part: torch.Tensor, out: torch.Tensor, step: Optional[torch.Tensor] = None,
+               sched: Optional[LrSchedule] = None) -> torch.Tensor:
+    """out[0] = Σ part (fixed order, fp64 accumulate); bumps ``step`` if given (and then, with ``sched``, writes the
+    rate of that update to ``sched.out``)."""
+    assert sched is None or step is not None, "a schedule is evaluated where the step counter is bumped"
     if not part.is_cuda:
         out.fill_(float(part.double().sum()))
         if step is not None:
             step.add_(1)
+        if sched is not None:
+            sched._write_cpu(step)
+        return out
+    if sched is not None:
+        N.check(N.lib().dtc_sum_finish_lr(part.data_ptr(), part.numel(), out.data_ptr(), N.ptr(step), *sched._args(),
+                                          N.stream_ptr(part.device)), "dtc_sum_finish_lr")
         return out
     N.check(N.lib().dtc_sum_finish(part.data_ptr(), part.numel(), out.data_ptr(), N.ptr(step),
                                    N.stream_ptr(part.device)), "dtc_sum_finish")
@@ -84,8 +133,11 @@ def sum_finish(part: torch.Tensor, out: torch.Tensor, step: Optional[torch.Tenso
 def adamw_flat(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
                mirror: Optional[torch.Tensor], n_mirror: int, step: torch.Tensor, sumsq: torch.Tensor,
                lr: float, b1: float, b2: float, eps: float, wd: float, max_norm: float,
-               enable: Optional[torch.Tensor] = None, max_blocks: int = 0):
+               enable: Optional[torch.Tensor] = None, max_blocks: int = 0, lr_dev: Optional[torch.Tensor] = None):
     """In-place AdamW on flat fp32 buffers; ``mirror[:n_mirror] = bf16(p[:n_mirror])``.
+
+    ``lr_dev`` (fp32 [1], optional): this update's scheduled rate (:class:`LrSchedule`), read on the device in place
+    of ``lr``.
 
     ``step`` (int64 [1], already incremented) gives t for the bias correction; ``sumsq``
     (fp32 [1]) is the global Σg² for the clip.  ``enable`` (fp32 [1], optional): the update is
@@ -98,6 +150,8 @@ def adamw_flat(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
         # the hyperparameters as the kernel gets them: fp32 roundings, 1 - b formed in fp32 (1 - 0.999 in double
         # rounds to an fp32 1.3e-5 away from 1.f - 0.999f)
         lr, b1, b2, eps, wd, mx = (torch.tensor(x, dtype=torch.float32) for x in (lr, b1, b2, eps, wd, max_norm))
+        if lr_dev is not None:
+            lr = lr_dev[0].float().clone()
         t = step[0].float()
         norm = sumsq[0].float().sqrt()
         scale = mx / norm if (max_norm > 0 and not bool(norm < mx)) else torch.tensor(1.0)
@@ -109,6 +163,11 @@ def adamw_flat(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
         p.sub_(lr * (mhat / (vhat.sqrt() + eps) + wd * p))
         if mirror is not None and n_mirror > 0:
             mirror[:n_mirror].copy_(p[:n_mirror])
+        return
+    if lr_dev is not None:
+        N.check(N.lib().dtc_adamw_lr(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), N.ptr(mirror), n, n_mirror,
+                                     step.data_ptr(), sumsq.data_ptr(), lr, b1, b2, eps, wd, max_norm, N.ptr(enable),
+                                     int(max_blocks), lr_dev.data_ptr(), N.stream_ptr(p.device)), "dtc_adamw_lr")
         return
     N.check(N.lib().dtc_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), N.ptr(mirror), n, n_mirror,
                               step.data_ptr(), sumsq.data_ptr(), lr, b1, b2, eps, wd, max_norm, N.ptr(enable),
@@ -224,7 +283,7 @@ def adamw_tr_plan(lo: int, hi: int, mats):
 
 def adamw_tr(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, mirror: torch.Tensor, n_mirror: int,
              plan, step: torch.Tensor, sumsq: torch.Tensor, lr: float, b1: float, b2: float, eps: float, wd: float,
-             max_norm: float):
+             max_norm: float, lr_dev: Optional[torch.Tensor] = None):
     """AdamW over the flat buffers (absolute offsets in ``plan``, :func:`adamw_tr_plan`) with the transposed
     bf16 mirror of the tiled weights written by the update itself (no separate transpose pass).  GPU only;
     bitwise equal to :func:`adamw_flat` + :func:`transpose_batch`."""
@@ -232,6 +291,12 @@ def adamw_tr(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
     assert L.dtc_aw_seg_bytes() == ctypes.sizeof(_AwSeg) and L.dtc_aw_task_bytes() == ctypes.sizeof(_AwtTask)
     assert L.dtc_aw_max_seg() == _AW_SEG_MAX and L.dtc_aw_max_tasks() == _AW_TASK_MAX
     for sb, tb in plan:
+        if lr_dev is not None:
+            N.check(L.dtc_adamw_tr_lr(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), mirror.data_ptr(),
+                                      n_mirror, ctypes.byref(sb), ctypes.byref(tb), step.data_ptr(), sumsq.data_ptr(),
+                                      lr, b1, b2, eps, wd, max_norm, lr_dev.data_ptr(), N.stream_ptr(p.device)),
+                    "dtc_adamw_tr_lr")
+            continue
         N.check(L.dtc_adamw_tr(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), mirror.data_ptr(), n_mirror,
                                ctypes.byref(sb), ctypes.byref(tb), step.data_ptr(), sumsq.data_ptr(), lr, b1, b2, eps,
                                wd, max_norm, N.stream_ptr(p.device)), "dtc_adamw_tr")

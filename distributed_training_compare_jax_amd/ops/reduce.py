@@ -80,6 +80,12 @@ class GradReducer:
         self.off += nbytes
         return t
 
+    def reserve(self):
+        """Allocate the arena now instead of at the first task (the engine does, with its other workspaces: what
+        it holds for good is then allocated when construction returns, and a step allocates only what it frees)."""
+        if self.arena is None:
+            self.arena = torch.empty(self.arena_bytes, dtype=torch.uint8, device=self.device)
+
     # ------------------------------------------------------------------ tasks
     def add_wide(self, src: torch.Tensor, dst: torch.Tensor, P: int, beta: float):
         """dst[:] = beta·dst + Σ_p src[p] (src [P, dst.numel()], contiguous)."""

@@ -108,6 +108,25 @@ class Engine:
                 why = "dp == 1 without a process group (the rehearsal needs one for the init handshake)"
             if why:
                 raise ValueError(f"dp_comm: p2p cannot be combined with {why}")
+        # grad_accum: k (the local batch as k microbatches inside one step, gradients accumulated in place): refused
+        # here, by name, what it does not cover
+        k_acc = train_cfg.grad_accum
+        if isinstance(k_acc, bool) or not isinstance(k_acc, int) or k_acc < 1:
+            raise ValueError(f"grad_accum={k_acc!r}: expected an integer >= 1")
+        if k_acc > 1:
+            why = None
+            if pp > 1:
+                why = (f"pp={pp} (a pipeline accumulates its own microbatches: set pp_microbatches, "
+                       "and leave grad_accum at 1)")
+            elif train_cfg.defer_optimizer:
+                why = ("defer_optimizer=true (the deferred update is launched under the first forward of the next "
+                       "step; it has not been run with more than one forward per step)")
+            elif train_cfg.batch % dp == 0 and (train_cfg.batch // dp) % k_acc:
+                why = (f"a local batch of {train_cfg.batch // dp} rows (batch {train_cfg.batch} / dp {dp}): it must "
+                       f"split into {k_acc} whole microbatches")
+            if why:
+                raise ValueError(f"grad_accum={k_acc} cannot be combined with {why}")
+        self.grad_accum = int(k_acc)
         # lm_head + CE split by vocab over the last two pipeline stages (models/gpt.py head_split_*): auto when
         # the head alone outweighs an even share of the model (GPT-2 small at pp >= 5: 2.9 blocks vs 14.9 / pp)
         hsplit = train_cfg.pp_head_split
@@ -166,9 +185,10 @@ class Engine:
         if self.global_batch % dp:
             raise ValueError(f"global batch {self.global_batch} not divisible by dp={dp}")
         self.b_local = self.global_batch // dp
-        self.n_micro = max(1, train_cfg.pp_microbatches) if pp > 1 else 1
+        self.n_micro = max(1, train_cfg.pp_microbatches) if pp > 1 else self.grad_accum
         if self.b_local % self.n_micro:
-            raise ValueError(f"local batch {self.b_local} not divisible by pp_microbatches={self.n_micro}")
+            raise ValueError(f"local batch {self.b_local} not divisible by "
+                             f"{'pp_microbatches' if pp > 1 else 'grad_accum'}={self.n_micro}")
         self.mb_rows = self.b_local // self.n_micro
         self.row0 = m.dp_idx * self.b_local
 
@@ -236,17 +256,20 @@ class Engine:
         self.tp_comm_dtype = tcd
         self.stage.tp_bf16 = bool(tp > 1 and tcd == "bf16")
         sp = train_cfg.tp_sequence_parallel
+        # (under grad_accum every microbatch must split into whole sequences over tp: mb_rows == b_local at k = 1)
+        sp_rows = self.mb_rows if pp == 1 else self.b_local
         if sp is None:  # auto: wherever it applies
-            sp = tp > 1 and pp == 1 and self.b_local % tp == 0
+            sp = tp > 1 and pp == 1 and sp_rows % tp == 0
         if sp:
             if tp == 1:
                 if dinfo.rank == 0:
                     warnings.warn("tp_sequence_parallel ignored: tp == 1")
             elif pp > 1:
                 raise ValueError("tp_sequence_parallel needs pp == 1 (one stage holds the embedding and the head)")
-            elif not self.stage.enable_sequence_parallel(self.b_local):
+            elif not self.stage.enable_sequence_parallel(sp_rows):
                 raise ValueError(f"tp_sequence_parallel: the local batch {self.b_local} must split into whole "
-                                 f"sequences over tp={tp}")
+                                 f"sequences over tp={tp}" + (f" in each of its {self.grad_accum} microbatches "
+                                                              f"of {self.mb_rows} rows" if self.grad_accum > 1 else ""))
         # deferred grouped weight gradients (models/gpt.py set_wgrad_group): all layers + the lm_head in
         # one launch when no collective waits on per-layer grads (dp == 1), else groups of wgrad_group
         # layers so each group's DP buckets go out under the next group's backward
@@ -358,6 +381,14 @@ class Engine:
             self.ids, self.labels, self.keys = self._dev_in[0], self._dev_in[1], self._dev_in[2].view(-1)
             self._host = [torch.zeros(3, self.feed_rows, T, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if self.grad_accum > 1:
+            # every microbatch's embedding-output gradient lands in its rows here; ONE embedding backward per step
+            # then runs over the whole local batch (beta 0, the host-sorted keys of the whole batch), so its fused
+            # grad-norm partials and sparse zeroing keep their one-writer invariant.  Under the DP embedding gather
+            # this is the gather's source (with its bf16 twin where the payload is bf16)
+            self.dh_acc = torch.zeros(self.b_local * T, D, dtype=torch.float32, device=self.device)
+            self.dh_acc_bf = (torch.zeros(self.b_local * T, D, dtype=torch.bfloat16, device=self.device)
+                              if self.embed_gather and self.dh_all_bf is not None else None)
         if train_cfg.dp_comm == "p2p":
             self._init_dp_p2p()
         elif self.zero_p2p:
@@ -428,8 +459,9 @@ class Engine:
         lnf = int(os.environ.get("DTC_LN_FUSE", "2"))
         # dp == 1 too: under DP the bucket all-reduces (RCCL kernels on other CUs) run during the
         # backward, and the in-launch row-statistics exchange needs all of its blocks co-resident.
+        # grad_accum == 1 too: a fused site is called once per step (its row-statistics epoch is the step counter)
         if (lnf and on_gpu and self.act_dtype == torch.bfloat16 and tp == 1 and pp == 1 and not self.dp_comm
-                and not self.defer_opt):
+                and not self.defer_opt and self.grad_accum == 1):
             has_wt = len(self.layout.layers) > 0 and self.flat.wt(f"h.{self.layout.layers[0]}.fc1.w") is not None
             self.stage.enable_ln_fusion(self.b_local * T, self.opt.step_t, fwd=bool(lnf & 1),
                                         bwd=bool(lnf & 2) and has_wt)
@@ -526,7 +558,7 @@ class Engine:
         device's memory, 1 GiB on CPU) the groups shrink to what fits (at least one layer)."""
         if n_layers == 0:
             return 0
-        tokens = self.b_local * self.T
+        tokens = (self.mb_rows if self.grad_accum > 1 else self.b_local) * self.T  # alive at once
         esize = 2 if self.act_dtype == torch.bfloat16 else 4
         D, F = mc.d_model, mc.d_ff
         per_layer = (8 * D + 2 * F) * tokens * esize
@@ -571,6 +603,8 @@ class Engine:
 
         # split-K slabs: the lm_head dgrad (fused CE, split 8 at the reference size) needs 67 MB
         reserve_workspace(self.device, 96 << 20)
+        if self.stage.red is not None:
+            self.stage.red.reserve()  # the batched-reduction arena: fixed size, held for the engine's lifetime
 
     @property
     def tokens_per_step(self) -> int:
@@ -697,7 +731,55 @@ class Engine:
                 L.dtc_gemm_set_wgrad256(self.prev[1])
                 L.dtc_gemm_set_r8(self.prev[2])
 
+    def _step_fn_accum(self):
+        """``grad_accum: k`` -- the step of :meth:`_step_fn_dp_tp` with the local batch as k microbatches.  Microstep j
+        runs rows [j·mb, (j+1)·mb) of the static inputs: the embedding forward with the global row offset of its
+        first row (the dropout mask of the unaccumulated step), the head with the full-batch loss scale
+        (accumulated into the loss from j = 1 on), the backward with the full-batch gradient scale and beta = 0
+        for j = 0, 1 after.  Its saved activations die with its ``ctx`` before the next forward.  Whatever means
+        "this gradient is final" -- bucket hooks, norm chunks, the embedding backward, the loss sum, the update --
+        belongs to the last microstep (:meth:`_backward_dp_tp` with ``micro``)."""
+        st, T, b, k, mb = self.stage, self.T, self.b_local, self.n_micro, self.mb_rows
+        dp, dpc, step = self.mesh.dp, self.dp_comm, self.opt.step_t
+        hk = self.keys if self.host_keys else None
+        out = None
+        for j in range(k):
+            last = j == k - 1
+            ctx: Dict = {}
+            r = slice(j * mb, (j + 1) * mb)
+            h = st.embed_forward(self.ids[r], step, self.row0 + j * mb, ctx, want_keys=False)
+            h = st.stage_forward(h, mb, ctx)
+            st.head_forward(h, self.labels[r], 1.0 / (b * T), ctx, loss_out=self.loss, accumulate=j > 0)
+            del h
+            gathered = None
+            if last:
+                if dpc:
+                    self._loss_allreduce(name="loss_dp")  # final after the last forward; under the last backward
+                if self.embed_gather:
+                    gathered = (self.ids_all, 0, (hk, None) if hk is not None else st.embed_keys(self.ids_all))
+                else:  # the one embedding backward of the step: the whole local batch
+                    full = (hk, None) if hk is not None else st.embed_keys(self.ids)
+                    ctx["embed"] = (self.ids, self.row0, full)
+                    if st.sp:  # its rows arrive gathered over the TP group already (per microstep, below)
+                        gathered = ctx["embed"]
+            # only the last backward runs under the bucket collectives
+            with self._CommSafeGemms(dpc and last and self.stage.flat.device.type == "cuda"):
+                out = self._backward_dp_tp(ctx, dp, step, gathered, micro=(j, k))
+            del ctx
+        return out
+
+    def _accum_dx(self, j: int, dx: torch.Tensor, dx_c: Optional[torch.Tensor] = None):
+        """Microstep j's embedding-output gradient into its rows of the full-batch buffer (``grad_accum``)."""
+        n = self.mb_rows * self.T
+        if self.stage.sp:
+            dx = self.tp_comm.all_gather_rows(dx)  # the microbatch's rows of every TP rank, in row order
+        self.dh_acc[j * n:(j + 1) * n].copy_(dx)
+        if self.dh_acc_bf is not None and dx_c is not None and dx_c.dtype == torch.bfloat16:
+            self.dh_acc_bf[j * n:(j + 1) * n].copy_(dx_c)
+
     def _step_fn_dp_tp(self):
+        if self.grad_accum > 1:
+            return self._step_fn_accum()
         st, T, b = self.stage, self.T, self.b_local
         self._launch_deferred_update()
         dp = self.mesh.dp
@@ -719,9 +801,20 @@ class Engine:
         with self._CommSafeGemms(dpc and self.stage.flat.device.type == "cuda"):  # bucket all-reduces overlap it
             return self._backward_dp_tp(ctx, dp, step, gathered)
 
-    def _backward_dp_tp(self, ctx, dp, step, gathered):
+    def _backward_dp_tp(self, ctx, dp, step, gathered, micro=None):
         st, T, b = self.stage, self.T, self.b_local
-        dx, dx_c = st.head_backward(ctx, grad_scale=1.0 / (b * T * dp), beta=0.0)
+        j, k = micro if micro is not None else (0, 1)  # grad_accum: microstep j of k (the scales stay full-batch)
+        beta = 0.0 if j == 0 else 1.0
+        if j < k - 1:
+            # not the last microstep: the gradients are partial sums.  No bucket, no norm chunk, no TP sum of the
+            # sequence-parallel partials (they are summed once, accumulated), no embedding backward, no update
+            st.sp_hold = st.sp
+            dx, dx_c = st.head_backward(ctx, grad_scale=1.0 / (b * T * dp), beta=beta)
+            dx, dx_c = st.stage_backward(ctx, dx, dx_c, beta)
+            st.sp_hold = False
+            self._accum_dx(j, dx, dx_c)
+            return self.loss
+        dx, dx_c = st.head_backward(ctx, grad_scale=1.0 / (b * T * dp), beta=beta)
         bk, opt = self.buckets, self.opt
         side = st.red  # grad-norm chunks: into the reducer's batched launches (None: computed right away)
         # deferred weight gradients: the head's grads are final only after the first grouped launch, so
@@ -761,6 +854,9 @@ class Engine:
             # the embedding-output gradients go out the moment the first layer's dgrad produces them,
             # under that layer's remaining weight-gradient work
             def dx_hook(d, d_c, out=self.dh_all, g=self.mesh.dp_group):
+                if k > 1:  # the gather's source is the whole local batch: this microbatch's rows complete it
+                    self._accum_dx(j, d, d_c)
+                    d, d_c = self.dh_acc, (self.dh_acc_bf if self.dh_acc_bf is not None else self.dh_acc)
                 if self.dh_all_bf is not None and d_c.dtype == torch.bfloat16:
                     out, d = self.dh_all_bf, d_c
                 ar = self.dp_p2p
@@ -769,7 +865,7 @@ class Engine:
                     return
                 self.program.comm(lambda: dist.all_gather_into_tensor(out, d, group=g),
                                   sig=csig("all_gather", g, d))
-        dx, dx_c = st.stage_backward(ctx, dx, dx_c, 0.0, hook=hook, dx_hook=dx_hook)
+        dx, dx_c = st.stage_backward(ctx, dx, dx_c, beta, hook=hook, dx_hook=dx_hook)
         if self.embed_gather:
             bk.ready_all()
             if self.dp_p2p is not None:  # the gather feeds the embedding backward; the buckets behind it do not
@@ -781,6 +877,9 @@ class Engine:
                 cast_bf16_to_f32(self.dh_all_bf, self.dh_all)
             st.embed_backward(ctx, self.dh_all, step, 0.0, gathered=gathered)
             opt.chunk_ready(len(opt.chunks) - 1, side)  # local wte/wpe grads: overlaps the tail bucket
+        elif k > 1:
+            self._accum_dx(j, dx, dx_c)
+            st.embed_backward(ctx, self.dh_acc, step, 0.0, gathered=gathered)  # (gathered: sequence parallel only)
         else:
             st.embed_backward(ctx, dx, step, 0.0)
         if self.zero_p2p:

@@ -136,7 +136,10 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
                   comm_ms_mean=float(np.mean(comm_ms)) if comm_ms else 0.0,
                   # model FLOPs (fwd+bwd matmuls + attention, ModelConfig.flops_per_token) / step time
                   tflops=model_config.flops_per_token() * eng.tokens_per_step * train_config.steps / max(total, 1e-9) / 1e12,
-                  world_size=dinfo.world)
+                  world_size=dinfo.world,
+                  # one optimizer update per step over the global batch, run as grad_accum microbatches per rank
+                  grad_accum=eng.grad_accum, microbatch_rows=eng.mb_rows,
+                  lr_schedule=opt_config.lr_schedule)
     result["tflops_per_gpu"] = result["tflops"] / max(1, dinfo.world)
     if tr.enabled:
         path = tr.write()

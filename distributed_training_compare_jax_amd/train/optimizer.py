@@ -80,6 +80,7 @@ class FusedAdamW:
         self.segments = O.make_segments(self._merged, dev)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.sched = O.LrSchedule.of(cfg, dev)  # lr_schedule: the rate of each update, written with the step bump
         self.chunks = []  # incremental-norm chunks: [segments, lo, hi, partial view, reducer tasks]
         self._done = []
         self.reducer = None  # GradReducer of the model stage (single-stream GPU backward)
@@ -174,12 +175,12 @@ class FusedAdamW:
                 self.chunk_ready(i, red)
             if red is not None:
                 red.flush_all()  # every remaining chunk in one launch
-            O.sum_finish(self.part, self.sumsq, step=self.step_t)
+            O.sum_finish(self.part, self.sumsq, step=self.step_t, sched=self.sched)
             self._done = [False] * len(self.chunks)
         else:
             if red is not None:
                 red.flush_all()  # grads must be final
-            O.sumsq_segments(f.grads, self.segments, self.sumsq, step=self.step_t)
+            O.sumsq_segments(f.grads, self.segments, self.sumsq, step=self.step_t, sched=self.sched)
         if self.tp_size > 1:
             if self.tp_comm is not None and self.tp_comm.p2p is not None:
                 self.tp_comm.all_reduce_(self.sumsq)  # in-graph one-shot (no graph cut)
@@ -209,13 +210,15 @@ class FusedAdamW:
             plan = self._aw_plans[key]
             if plan is not None:
                 O.adamw_tr(f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.mirror, f.n_mirror, plan, self.step_t,
-                           self.sumsq, c.lr, c.b1, c.b2, c.eps, c.weight_decay, c.grad_clip)
+                           self.sumsq, c.lr, c.b1, c.b2, c.eps, c.weight_decay, c.grad_clip,
+                           lr_dev=O._lr_dev(self.sched))
                 f.refresh_fp8(lo, hi)
                 f.refresh_mxfp8(lo, hi)
                 return
         O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[lo:hi], f.exp_avg_sq[lo:hi],
                      f.mirror[lo:lo + max(nm, 4)] if nm > 0 else None, nm, self.step_t, self.sumsq, c.lr, c.b1, c.b2,
-                     c.eps, c.weight_decay, c.grad_clip, enable=enable, max_blocks=max_blocks)
+                     c.eps, c.weight_decay, c.grad_clip, enable=enable, max_blocks=max_blocks,
+                     lr_dev=O._lr_dev(self.sched))
         if nm > 0:
             f.refresh_transposed(lo, hi)
         f.refresh_fp8(lo, hi)
@@ -227,6 +230,14 @@ class FusedAdamW:
 
     def grad_norm(self) -> float:
         return float(self.sumsq.item()) ** 0.5
+
+    def lr_at(self, t: int) -> float:
+        """The rate of update ``t`` (the already-incremented step counter) in float64 (``OptimConfig.lr_at``)."""
+        return self.cfg.lr_at(t)
+
+    def lr_value(self) -> float:
+        """Blocking read of the rate the last update used: the device scalar under a schedule, else ``cfg.lr``."""
+        return float(self.sched.out.item()) if self.sched is not None else float(self.cfg.lr)
 
 
 class P2PShardedAdamW:
@@ -266,6 +277,7 @@ class P2PShardedAdamW:
         self._sq4 = torch.zeros(4, dtype=torch.float32, device=dev)  # the sum moves 16-byte pieces
         self.sumsq = self._sq4[:1]
         self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.sched = O.LrSchedule.of(cfg, dev)  # lr_schedule: the rate of each update, written with the step bump
         self.reducer = None
         self.peer = None
         self.plan_hash = None
@@ -286,14 +298,14 @@ class P2PShardedAdamW:
     def step(self):
         """After every bucket's reduce-scatter has been joined to the current stream."""
         f, c, peer = self.flat, self.cfg, self.peer
-        O.sum_finish(self.part, self.sumsq, step=self.step_t)
+        O.sum_finish(self.part, self.sumsq, step=self.step_t, sched=self.sched)
         peer.on_comm(lambda: peer.all_reduce_(self._sq4))
         peer.join()
         for (lo, hi), off in zip(self.owned, self.offsets):
             if hi > lo:
                 O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[off:off + hi - lo],
                              f.exp_avg_sq[off:off + hi - lo], None, 0, self.step_t, self.sumsq, c.lr, c.b1, c.b2,
-                             c.eps, c.weight_decay, c.grad_clip)
+                             c.eps, c.weight_decay, c.grad_clip, lr_dev=O._lr_dev(self.sched))
         nm = f.n_mirror if f.use_mirror else 0
 
         def gathers():
@@ -311,6 +323,14 @@ class P2PShardedAdamW:
 
     def grad_norm(self) -> float:
         return float(self.sumsq.item()) ** 0.5
+
+    def lr_at(self, t: int) -> float:
+        """The rate of update ``t`` (the already-incremented step counter) in float64 (``OptimConfig.lr_at``)."""
+        return self.cfg.lr_at(t)
+
+    def lr_value(self) -> float:
+        """Blocking read of the rate the last update used: the device scalar under a schedule, else ``cfg.lr``."""
+        return float(self.sched.out.item()) if self.sched is not None else float(self.cfg.lr)
 
 
 class ShardedAdamW:
@@ -349,6 +369,7 @@ class ShardedAdamW:
         self.segments = O.make_segments(segs, dev)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.sched = O.LrSchedule.of(cfg, dev)  # lr_schedule: the rate of each update, written with the step bump
         self.reducer = None
         # gloo on device tensors (the 2-ranks-on-one-GPU test rig) lacks the in-place tensor
         # collectives: emulate them with all_reduce / list all_gather (same results)
@@ -359,7 +380,8 @@ class ShardedAdamW:
         if hi <= lo:
             return
         O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[mlo:mlo + hi - lo], f.exp_avg_sq[mlo:mlo + hi - lo],
-                     None, 0, self.step_t, self.sumsq, c.lr, c.b1, c.b2, c.eps, c.weight_decay, c.grad_clip)
+                     None, 0, self.step_t, self.sumsq, c.lr, c.b1, c.b2, c.eps, c.weight_decay, c.grad_clip,
+                     lr_dev=O._lr_dev(self.sched))
 
     def step(self):
         if self.reducer is not None:
@@ -374,7 +396,7 @@ class ShardedAdamW:
                               sig=csig("reduce_scatter", grp, g[:n]))
         if self.n_tail:
             self.program.comm(lambda: dist.all_reduce(g[n:], group=grp), sig=csig("all_reduce", grp, g[n:]))
-        O.sumsq_segments(g, self.segments, self.sumsq, step=self.step_t)
+        O.sumsq_segments(g, self.segments, self.sumsq, step=self.step_t, sched=self.sched)
         s = self.sumsq
         self.program.comm(lambda: dist.all_reduce(s, group=grp), sig=csig("all_reduce", grp, s))
         self._adamw(lo, hi, 0)
@@ -391,3 +413,11 @@ class ShardedAdamW:
 
     def grad_norm(self) -> float:
         return float(self.sumsq.item()) ** 0.5
+
+    def lr_at(self, t: int) -> float:
+        """The rate of update ``t`` (the already-incremented step counter) in float64 (``OptimConfig.lr_at``)."""
+        return self.cfg.lr_at(t)
+
+    def lr_value(self) -> float:
+        """Blocking read of the rate the last update used: the device scalar under a schedule, else ``cfg.lr``."""
+        return float(self.sched.out.item()) if self.sched is not None else float(self.cfg.lr)

@@ -42,6 +42,7 @@ def save(eng, output_dir: str, step: int):
     meta = dict(step=step, dp=m.dp, tp=m.tp, pp=m.pp, rank=m.rank, dp_idx=m.dp_idx, tp_idx=m.tp_idx,
                 pp_idx=m.pp_idx, slots=slots, model=eng.mcfg.name,
                 zero_stage=int(getattr(eng, "zero", False)), **_zero_meta(eng),
+                lr_schedule=eng.ocfg.schedule_key(),
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
                 vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab))
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
@@ -112,6 +113,12 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
             if ck["zero_plan"] != now["zero_plan"]:
                 raise ValueError(f"zero_comm: p2p checkpoint plan {str(ck['zero_plan'])[:12]} differs from this run's "
                                  f"{str(now['zero_plan'])[:12]} (zero_plan): the ownership plan changed")
+    # the rate of every later update is a function of the saved step counter and these fields alone: a resume
+    # under other fields would silently continue on another curve (checkpoints from before the field: constant)
+    sched_ck, sched_now = m0.get("lr_schedule", "constant:0:0:0.0"), eng.ocfg.schedule_key()
+    if sched_ck != sched_now:
+        raise ValueError(f"checkpoint was written under lr_schedule {sched_ck} (name:warmup:decay:min_ratio), this run "
+                         f"has {sched_now}: resume with the schedule fields that wrote it")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
     for r, m in metas.items():
