@@ -38,6 +38,68 @@ struct PeerTable {
 
 __device__ __forceinline__ uint64_t wall_clock() { return __builtin_amdgcn_s_memrealtime(); }  // 100 MHz
 
+// error word of a timed-out wait = base + the rank (barrier) or flag word (stream flags, stage messages) waited for
+constexpr int ERR_BARRIER = 1000, ERR_FLAG = 2000, ERR_PP = 3000;
+
+// The bounded spin of every wait here: until *flag >= e (acquire at SCOPE, s_sleep(SLEEP) between polls); after
+// ~10 s it stores `code` into the error word and gives up, so the caller proceeds
+template <int SCOPE, int SLEEP>
+__device__ __forceinline__ void spin_until(const uint32_t* flag, uint32_t e, int* err, int code) {
+  const uint64_t t0 = wall_clock();
+  while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, SCOPE) < e) {
+    __builtin_amdgcn_s_sleep(SLEEP);
+    if (wall_clock() - t0 > 1000000000ull) {  // ~10 s at 100 MHz
+      atomicExch(err, code);
+      break;
+    }
+  }
+}
+
+// The rank-order sums every replica computes alike.  fp32: s = x[0]; s += x[p].  bf16: a = 0; a += float(x[p])
+// (the caller rounds a once, or not at all).  Each over the peers' halves at byte offset `off`, piece i, or over
+// pieces already in registers (v[p], p < world <= N).
+__device__ __forceinline__ void add8(float (&a)[8], const bf16x8& v) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) a[e] += (float)v[e];
+}
+
+__device__ __forceinline__ f32x4 rank_sum_f32(const PeerTable& t, long off, long i, int world) {
+  f32x4 s = ((const f32x4*)(t.base[0] + off))[i];
+  for (int p = 1; p < world; ++p) s += ((const f32x4*)(t.base[p] + off))[i];
+  return s;
+}
+
+template <int N>
+__device__ __forceinline__ f32x4 rank_sum_f32(const f32x4 (&v)[N], int world) {
+  f32x4 s = v[0];
+#pragma unroll
+  for (int p = 1; p < N; ++p)
+    if (p < world) s += v[p];
+  return s;
+}
+
+__device__ __forceinline__ void rank_sum_bf16(float (&a)[8], const PeerTable& t, long off, long i, int world) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) a[e] = 0.f;
+  for (int p = 0; p < world; ++p) add8(a, ((const bf16x8*)(t.base[p] + off))[i]);
+}
+
+template <int N>
+__device__ __forceinline__ void rank_sum_bf16(float (&a)[8], const bf16x8 (&v)[N], int world) {
+  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (a local: 2 VGPRs fewer in dp_reduce_shard_kernel<true>)
+#pragma unroll
+  for (int p = 0; p < N; ++p)
+    if (p < world) add8(s, v[p]);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) a[e] = s[e];
+}
+
+// the exact fp32 images (bits << 16) of the 8 bf16 values of a 16-byte piece: lo = values 0 .. 3, hi = 4 .. 7
+__device__ __forceinline__ void widen_bf16x8(const u32x4& v, u32x4& lo, u32x4& hi) {
+  lo = u32x4{v[0] << 16, v[0] & 0xffff0000u, v[1] << 16, v[1] & 0xffff0000u};
+  hi = u32x4{v[2] << 16, v[2] & 0xffff0000u, v[3] << 16, v[3] & 0xffff0000u};
+}
+
 // inc: 1 per barrier of the two-shot call (2 barriers), 2 for the one-shot call's single barrier, so
 // every call advances the epoch by 2 and the buffer half stays (epoch >> 1) & 1 at the call's start
 __global__ void p2p_barrier_kernel(PeerTable t, int rank, int world, uint32_t* __restrict__ epoch,
@@ -49,27 +111,20 @@ __global__ void p2p_barrier_kernel(PeerTable t, int rank, int world, uint32_t* _
   if (p < world && p != rank) {
     uint32_t* peer_flag = (uint32_t*)t.base[p] + rank;
     __hip_atomic_store(peer_flag, e, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    const uint32_t* mine = (const uint32_t*)t.base[rank] + p;
-    const uint64_t t0 = wall_clock();
-    while (__hip_atomic_load(mine, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < e) {
-      __builtin_amdgcn_s_sleep(2);
-      if (wall_clock() - t0 > 1000000000ull) {  // ~10 s at 100 MHz
-        atomicExch(err, 1000 + p);
-        break;
-      }
-    }
+    spin_until<__HIP_MEMORY_SCOPE_SYSTEM, 2>((const uint32_t*)t.base[rank] + p, e, err, ERR_BARRIER + p);
   }
   __syncthreads();
   if (p == 0) epoch[0] = e;
 }
 
-// copy x into own half h (h read from the epoch counter parity: 2 barriers per call)
-__global__ void p2p_stage_kernel(const f32x4* __restrict__ x, PeerTable t, int rank, long n4, long half_bytes,
-                                 const uint32_t* __restrict__ epoch) {
+// copy n16 16-byte pieces of x (any element type) into own half h at piece offset `at` (h read from the epoch
+// counter parity: 2 barriers per call): a whole message at 0, or the all-gather's slot
+__global__ void p2p_stage16_kernel(const u32x4* __restrict__ x, PeerTable t, int rank, long at, long n16,
+                                   long half_bytes, const uint32_t* __restrict__ epoch) {
   const int h = (epoch[0] >> 1) & 1;
-  DTC_ASSERT(16 * n4 <= half_bytes && rank >= 0);
-  f32x4* dst = (f32x4*)(t.base[rank] + FLAG_BYTES + h * half_bytes);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) dst[i] = x[i];
+  DTC_ASSERT(16 * (at + n16) <= half_bytes && rank >= 0);
+  u32x4* dst = (u32x4*)(t.base[rank] + FLAG_BYTES + h * half_bytes) + at;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) dst[i] = x[i];
 }
 
 __global__ void p2p_reduce_scatter_kernel(PeerTable t, int rank, int world, long n4, long half_bytes,
@@ -79,11 +134,8 @@ __global__ void p2p_reduce_scatter_kernel(PeerTable t, int rank, int world, long
   const long lo = rank * chunk, hi = min(n4, lo + chunk);
   const long off = FLAG_BYTES + h * half_bytes;
   DTC_ASSERT(16 * n4 <= half_bytes && rank < world);
-  for (long i = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (long)gridDim.x * blockDim.x) {
-    f32x4 s = ((const f32x4*)(t.base[0] + off))[i];
-    for (int p = 1; p < world; ++p) s += ((const f32x4*)(t.base[p] + off))[i];
-    ((f32x4*)(t.base[rank] + off))[i] = s;
-  }
+  for (long i = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (long)gridDim.x * blockDim.x)
+    ((f32x4*)(t.base[rank] + off))[i] = rank_sum_f32(t, off, i, world);
 }
 
 __global__ void p2p_all_gather_kernel(PeerTable t, int world, long n4, long half_bytes, f32x4* __restrict__ out,
@@ -107,11 +159,8 @@ __global__ void p2p_oneshot_kernel(PeerTable t, int world, long n4, long half_by
   const int h = ((epoch[0] - 2) >> 1) & 1;
   const long off = FLAG_BYTES + h * half_bytes;
   DTC_ASSERT(16 * n4 <= half_bytes && world >= 1);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    f32x4 s = ((const f32x4*)(t.base[0] + off))[i];
-    for (int p = 1; p < world; ++p) s += ((const f32x4*)(t.base[p] + off))[i];
-    out[i] = s;
-  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+    out[i] = rank_sum_f32(t, off, i, world);
 }
 
 // ---------------------------------------------------------------- bf16 payload (tp_comm_dtype: bf16)
@@ -120,18 +169,6 @@ __global__ void p2p_oneshot_kernel(PeerTable t, int world, long n4, long half_by
 //   out[i] = resid[i] + bias[i % ncols] + sum_p partial_p[i]
 // so the residual stream itself is never rounded (only the layer's delta is, once, to bf16).  The
 // two-shot reduce-scatter stores its reduced slice in bf16 (the all-gather reads half the bytes).
-__global__ void p2p_stage_bf16_kernel(const bf16x8* __restrict__ x, PeerTable t, int rank, long n8, long half_bytes,
-                                      const uint32_t* __restrict__ epoch) {
-  const int h = (epoch[0] >> 1) & 1;
-  DTC_ASSERT(16 * n8 <= half_bytes && rank >= 0);
-  bf16x8* dst = (bf16x8*)(t.base[rank] + FLAG_BYTES + h * half_bytes);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) dst[i] = x[i];
-}
-
-__device__ __forceinline__ void add8(float (&a)[8], const bf16x8& v) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) a[e] += (float)v[e];
-}
 
 // out (fp32) = resid + bias + the 8 values a, for elements 8i .. 8i+7
 __device__ __forceinline__ void finish8(float (&a)[8], long i, float* __restrict__ out, const float* __restrict__ resid,
@@ -157,8 +194,8 @@ __global__ void p2p_oneshot_bf16_kernel(PeerTable t, int world, long n8, long ha
   const long off = FLAG_BYTES + h * half_bytes;
   DTC_ASSERT(16 * n8 <= half_bytes && world >= 1 && ncols % 8 == 0);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < world; ++p) add8(a, ((const bf16x8*)(t.base[p] + off))[i]);
+    float a[8];
+    rank_sum_bf16(a, t, off, i, world);
     finish8(a, i, out, resid, bias, ncols);
   }
 }
@@ -171,8 +208,8 @@ __global__ void p2p_reduce_scatter_bf16_kernel(PeerTable t, int rank, int world,
   const long off = FLAG_BYTES + h * half_bytes;
   DTC_ASSERT(16 * n8 <= half_bytes && rank < world);
   for (long i = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (long)gridDim.x * blockDim.x) {
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < world; ++p) add8(a, ((const bf16x8*)(t.base[p] + off))[i]);
+    float a[8];
+    rank_sum_bf16(a, t, off, i, world);
     bf16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = f2bf(a[e]);
@@ -188,8 +225,9 @@ __global__ void p2p_all_gather_bf16_kernel(PeerTable t, int world, long n8, long
   const long off = FLAG_BYTES + h * half_bytes;
   DTC_ASSERT(16 * n8 <= half_bytes && world >= 1 && ncols % 8 == 0);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    add8(a, ((const bf16x8*)(t.base[(int)(i / chunk)] + off))[i]);
+    const bf16x8 v[1] = {((const bf16x8*)(t.base[(int)(i / chunk)] + off))[i]};  // the slice owner's reduced piece
+    float a[8];
+    rank_sum_bf16(a, v, 1);
     finish8(a, i, out, resid, bias, ncols);
   }
 }
@@ -213,10 +251,10 @@ __global__ void p2p_rs_kernel(PeerTable t, int rank, int world, long n8_loc, lon
   DTC_ASSERT(rank < world && (BF16 ? 16 : 32) * n8_loc * world <= half_bytes && (!bias || ncols % 8 == 0));
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8_loc; i += (long)gridDim.x * blockDim.x) {
     float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < world; ++p) {
-      if constexpr (BF16) {
-        add8(a, ((const bf16x8*)(t.base[p] + off))[lo8 + i]);
-      } else {
+    if constexpr (BF16) {
+      rank_sum_bf16(a, t, off, lo8 + i, world);
+    } else {  // fp32 partials: summed from 0 like the bf16 ones (not from x[0])
+      for (int p = 0; p < world; ++p) {
         const f32x4* src = (const f32x4*)(t.base[p] + off) + 2 * (lo8 + i);
         const f32x4 v0 = src[0], v1 = src[1];
 #pragma unroll
@@ -225,15 +263,6 @@ __global__ void p2p_rs_kernel(PeerTable t, int rank, int world, long n8_loc, lon
     }
     finish8(a, i, out, resid, bias, ncols);  // i indexes this rank's rows: column = (8 i) % ncols
   }
-}
-
-// stage n16 16-byte pieces of x into own half at piece offset `at` (the all-gather's slot / a full partial)
-__global__ void p2p_stage16_kernel(const u32x4* __restrict__ x, PeerTable t, int rank, long at, long n16,
-                                   long half_bytes, const uint32_t* __restrict__ epoch) {
-  const int h = (epoch[0] >> 1) & 1;
-  DTC_ASSERT(16 * (at + n16) <= half_bytes && rank >= 0);
-  u32x4* dst = (u32x4*)(t.base[rank] + FLAG_BYTES + h * half_bytes) + at;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) dst[i] = x[i];
 }
 
 // all-gather: out[q * n16_loc + i] = rank q's slot (16-byte pieces, any element type); own slot local
@@ -281,17 +310,7 @@ __global__ void pp_signal_kernel(uint32_t* __restrict__ peer_flags, int flag_idx
 __global__ void pp_wait_kernel(const uint32_t* __restrict__ flags, int flag_idx, const uint32_t* __restrict__ epoch,
                                int* __restrict__ err) {
   DTC_ASSERT(flag_idx >= 0 && flag_idx < FLAG_BYTES / 4);
-  if (threadIdx.x == 0) {
-    const uint32_t e = epoch[0];
-    const uint64_t t0 = wall_clock();
-    while (__hip_atomic_load(flags + flag_idx, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < e) {
-      __builtin_amdgcn_s_sleep(2);
-      if (wall_clock() - t0 > 1000000000ull) {  // ~10 s at 100 MHz
-        atomicExch(err, 3000 + flag_idx);
-        break;
-      }
-    }
-  }
+  if (threadIdx.x == 0) spin_until<__HIP_MEMORY_SCOPE_SYSTEM, 2>(flags + flag_idx, epoch[0], err, ERR_PP + flag_idx);
   __syncthreads();
 }
 
@@ -304,10 +323,7 @@ __global__ void pp_pull_kernel(const u32x4* __restrict__ slot, u32x4* __restrict
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) {
     const u32x4 v = slot[i];
     out[i] = v;
-    if constexpr (F32) {
-      out_f32[2 * i] = u32x4{v[0] << 16, v[0] & 0xffff0000u, v[1] << 16, v[1] & 0xffff0000u};
-      out_f32[2 * i + 1] = u32x4{v[2] << 16, v[2] & 0xffff0000u, v[3] << 16, v[3] & 0xffff0000u};
-    }
+    if constexpr (F32) widen_bf16x8(v, out_f32[2 * i], out_f32[2 * i + 1]);
   }
 }
 
@@ -379,6 +395,22 @@ __global__ void __launch_bounds__(256) dp_pack_kernel(const float* __restrict__ 
   }
 }
 
+// The load phase of dp_reduce_kernel and dp_reduce_shard_kernel: all W peers' loads of DP_RU pieces (i0 + u stride,
+// below hi) before the first add
+template <class V>
+__device__ __forceinline__ void dp_load_peers(V (&v)[DP_RU][P2P_MAX], const PeerTable& t, long off, long i0,
+                                              long stride, long hi, int world) {
+#pragma unroll
+  for (int u = 0; u < DP_RU; ++u) {
+    const long i = i0 + u * stride;
+    if (i < hi) {
+#pragma unroll
+      for (int p = 0; p < P2P_MAX; ++p)
+        if (p < world) v[u][p] = ((const V*)(t.base[p] + off))[i];
+    }
+  }
+}
+
 template <bool BF16>
 __global__ void __launch_bounds__(256) dp_reduce_kernel(PeerTable t, int rank, int world, long pieces, long half_bytes,
                                                         const uint32_t* __restrict__ epoch) {
@@ -392,34 +424,20 @@ __global__ void __launch_bounds__(256) dp_reduce_kernel(PeerTable t, int rank, i
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i0 = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < hi; i0 += DP_RU * stride) {
     V v[DP_RU][P2P_MAX];
-#pragma unroll
-    for (int u = 0; u < DP_RU; ++u) {
-      const long i = i0 + u * stride;
-      if (i < hi) {
-#pragma unroll
-        for (int p = 0; p < P2P_MAX; ++p)
-          if (p < world) v[u][p] = ((const V*)(t.base[p] + off))[i];
-      }
-    }
+    dp_load_peers(v, t, off, i0, stride, hi, world);
 #pragma unroll
     for (int u = 0; u < DP_RU; ++u) {
       const long i = i0 + u * stride;
       if (i < hi) {
         if constexpr (BF16) {
-          float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int p = 0; p < P2P_MAX; ++p)
-            if (p < world) add8(a, v[u][p]);
+          float a[8];
+          rank_sum_bf16(a, v[u], world);
           bf16x8 o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = f2bf(a[e]);
           ((bf16x8*)(t.base[rank] + off))[i] = o;
         } else {
-          f32x4 s = v[u][0];
-#pragma unroll
-          for (int p = 1; p < P2P_MAX; ++p)
-            if (p < world) s += v[u][p];
-          ((f32x4*)(t.base[rank] + off))[i] = s;
+          ((f32x4*)(t.base[rank] + off))[i] = rank_sum_f32(v[u], world);
         }
       }
     }
@@ -453,9 +471,10 @@ __global__ void __launch_bounds__(256) dp_gather_kernel(PeerTable t, int world, 
       if (i < pieces) {
         if constexpr (BF16) {
           DTC_ASSERT(8 * i + 4 <= n);
-          out4[2 * i] = u32x4{v[u][0] << 16, v[u][0] & 0xffff0000u, v[u][1] << 16, v[u][1] & 0xffff0000u};
-          if (8 * i + 4 < n)  // the last piece of n % 8 == 4 holds 4 elements: never write past out + n
-            out4[2 * i + 1] = u32x4{v[u][2] << 16, v[u][2] & 0xffff0000u, v[u][3] << 16, v[u][3] & 0xffff0000u};
+          u32x4 hi;
+          widen_bf16x8(v[u], out4[2 * i], hi);
+          // the last piece of n % 8 == 4 holds 4 elements: never write past out + n
+          if (8 * i + 4 < n) out4[2 * i + 1] = hi;
         } else {
           out4[i] = v[u];
         }
@@ -469,8 +488,9 @@ __global__ void __launch_bounds__(256) dp_gather_kernel(PeerTable t, int world, 
 // the updated parameters instead of the gradients.
 //
 //   reduce-scatter   pack (dp_pack_kernel, as is) -> barrier (+2) -> dp_reduce_shard_kernel: the loads and the sums
-//                    of dp_reduce_kernel, but the result goes as fp32 straight into grads[own slice] (bf16 widened
-//                    exactly), so those elements hold bit for bit what dtc_dp_allreduce would have left there, and
+//                    of dp_reduce_kernel (dp_load_peers, rank_sum_*), but the result goes as fp32 straight into
+//                    grads[own slice] (bf16 widened exactly), so those elements hold bit for bit what
+//                    dtc_dp_allreduce would have left there, and
 //                    the slice's sum of squares goes to one partial per block (fixed order: per thread in loop
 //                    order, the wave by xor shuffles, the 4 waves through LDS in wave order; no atomics)
 //   parameter gather pack of the owned fp32 parameter slice, compact at the start of the half -> barrier (+2) ->
@@ -504,24 +524,14 @@ __global__ void __launch_bounds__(256) dp_reduce_shard_kernel(PeerTable t, int r
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i0 = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < hi; i0 += DP_RU * stride) {
     V v[DP_RU][P2P_MAX];
-#pragma unroll
-    for (int u = 0; u < DP_RU; ++u) {
-      const long i = i0 + u * stride;
-      if (i < hi) {
-#pragma unroll
-        for (int p = 0; p < P2P_MAX; ++p)
-          if (p < world) v[u][p] = ((const V*)(t.base[p] + off))[i];
-      }
-    }
+    dp_load_peers(v, t, off, i0, stride, hi, world);
 #pragma unroll
     for (int u = 0; u < DP_RU; ++u) {
       const long i = i0 + u * stride;
       if (i < hi) {
         if constexpr (BF16) {
-          float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int p = 0; p < P2P_MAX; ++p)
-            if (p < world) add8(a, v[u][p]);
+          float a[8];
+          rank_sum_bf16(a, v[u], world);
 #pragma unroll
           for (int e = 0; e < 8; ++e) a[e] = (float)f2bf(a[e]);  // one rounding; the widening is exact
           DTC_ASSERT(8 * i + 4 <= n);
@@ -534,10 +544,7 @@ __global__ void __launch_bounds__(256) dp_reduce_shard_kernel(PeerTable t, int r
             for (int e = 4; e < 8; ++e) sq = fmaf(a[e], a[e], sq);
           }
         } else {
-          f32x4 s = v[u][0];
-#pragma unroll
-          for (int p = 1; p < P2P_MAX; ++p)
-            if (p < world) s += v[u][p];
+          const f32x4 s = rank_sum_f32(v[u], world);
           DTC_ASSERT(4 * i + 4 <= n);
           g4[i] = s;
 #pragma unroll
@@ -640,17 +647,7 @@ __global__ void flag_set_kernel(uint32_t* __restrict__ flags, int k, const uint3
 
 __global__ void flag_wait_kernel(const uint32_t* __restrict__ flags, int k, const uint32_t* __restrict__ epoch,
                                  int* __restrict__ err) {
-  if (threadIdx.x == 0) {
-    const uint32_t e = epoch[0];
-    const uint64_t t0 = wall_clock();
-    while (__hip_atomic_load(flags + k, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < e) {
-      __builtin_amdgcn_s_sleep(1);
-      if (wall_clock() - t0 > 1000000000ull) {
-        atomicExch(err, 2000 + k);
-        break;
-      }
-    }
-  }
+  if (threadIdx.x == 0) spin_until<__HIP_MEMORY_SCOPE_AGENT, 1>(flags + k, epoch[0], err, ERR_FLAG + k);
   __syncthreads();
 }
 
@@ -668,25 +665,64 @@ __global__ void cu_hog_kernel(uint64_t ticks, int* __restrict__ sink) {
   if (threadIdx.x == 0 && hog_lds[1] == 12345) sink[0] = 1;  // never true: keeps the LDS allocation live
 }
 
+// ---------------------------------------------------------------- host-side helpers of the entry points
+inline PeerTable make_peer_table(void* const* bases, int world) {
+  PeerTable t;
+  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
+  return t;
+}
+
+// blocks of 256 threads for n items, one each, at least 1 and at most cap
+inline int grid_for(long n, long cap = 1024) { return (int)std::min(cap, std::max(1L, (n + 255) / 256)); }
+
+// launch, and return a launch error from the entry point
+#define P2P_LAUNCH(K, blocks, threads, st, ...)                             \
+  do {                                                                      \
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(threads), 0, st, __VA_ARGS__); \
+    DTC_CHECK_LAUNCH();                                                     \
+  } while (0)
+// ... K<true> or K<false> (mostly: a bf16 payload or not), 256 threads
+#define P2P_LAUNCH_IF(flag, K, blocks, st, ...)                    \
+  do {                                                             \
+    if (flag) P2P_LAUNCH(K<true>, blocks, 256, st, __VA_ARGS__);   \
+    else P2P_LAUNCH(K<false>, blocks, 256, st, __VA_ARGS__);       \
+  } while (0)
+
+// The launches of an all-reduce of `pieces` 16-byte pieces, fp32 and bf16 alike: the stage copy of x (if any), then
+// one-shot (barrier + 2, `oneshot`) or two-shot (barrier, `reduce_scatter` over pieces / W, barrier, `all_gather`).
+// Both finishing kernels take (t, world, pieces, half_bytes, tail...).
+template <class RS, class Fin, class... Tail>
+int allreduce_launches(RS* reduce_scatter, Fin* oneshot, Fin* all_gather, const void* x, long pieces, bool one,
+                       const PeerTable& t, int rank, int world, long half_bytes, uint32_t* epoch, int* err,
+                       hipStream_t st, Tail... tail) {
+  const int blocks = grid_for(pieces);
+  if (x) P2P_LAUNCH(p2p_stage16_kernel, blocks, 256, st, (const u32x4*)x, t, rank, 0L, pieces, half_bytes, epoch);
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, one ? 2 : 1);
+  if (!one) {
+    P2P_LAUNCH(reduce_scatter, grid_for(pieces / world), 256, st, t, rank, world, pieces, half_bytes, epoch);
+    P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, 1);
+  }
+  Fin* finish = one ? oneshot : all_gather;
+  P2P_LAUNCH(finish, blocks, 256, st, t, world, pieces, half_bytes, tail...);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int dtc_epoch_inc(uint32_t* epoch, hipStream_t st) {
-  hipLaunchKernelGGL(epoch_inc_kernel, dim3(1), dim3(64), 0, st, epoch);
-  DTC_CHECK_LAUNCH();
+  P2P_LAUNCH(epoch_inc_kernel, 1, 64, st, epoch);
   return 0;
 }
 
 int dtc_flag_set(uint32_t* flags, int k, const uint32_t* epoch, hipStream_t st) {
-  hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(64), 0, st, flags, k, epoch);
-  DTC_CHECK_LAUNCH();
+  P2P_LAUNCH(flag_set_kernel, 1, 64, st, flags, k, epoch);
   return 0;
 }
 
 int dtc_flag_wait(const uint32_t* flags, int k, const uint32_t* epoch, int* err, hipStream_t st) {
-  hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, st, flags, k, epoch, err);
-  DTC_CHECK_LAUNCH();
+  P2P_LAUNCH(flag_wait_kernel, 1, 64, st, flags, k, epoch, err);
   return 0;
 }
 
@@ -738,33 +774,10 @@ inline bool oneshot_auto(long bytes, int world) {
 int dtc_p2p_allreduce(const float* x, float* out, long n, void* const* bases, int rank, int world, long half_bytes,
                       uint32_t* epoch, int* err, int mode, hipStream_t st) {
   if (world < 1 || world > P2P_MAX || n % 4 || n * 4 > half_bytes) return 4001;
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
-  const long n4 = n / 4;
-  const int blocks = (int)std::min(1024L, std::max(1L, (n4 + 255) / 256));
   const bool one = mode == 2 || (mode == 0 && oneshot_auto(n * 4, world));
-  hipLaunchKernelGGL(p2p_stage_kernel, dim3(blocks), dim3(256), 0, st, (const f32x4*)x, t, rank, n4, half_bytes, epoch);
-  DTC_CHECK_LAUNCH();
-  if (one) {
-    hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
-    DTC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(p2p_oneshot_kernel, dim3(blocks), dim3(256), 0, st, t, world, n4, half_bytes, (f32x4*)out,
-                       epoch);
-    DTC_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 1);
-  DTC_CHECK_LAUNCH();
-  const int rs_blocks = (int)std::min(1024L, std::max(1L, (n4 / world + 255) / 256));
-  hipLaunchKernelGGL(p2p_reduce_scatter_kernel, dim3(rs_blocks), dim3(256), 0, st, t, rank, world, n4, half_bytes,
-                     epoch);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 1);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_all_gather_kernel, dim3(blocks), dim3(256), 0, st, t, world, n4, half_bytes, (f32x4*)out,
-                     epoch);
-  DTC_CHECK_LAUNCH();
-  return 0;
+  return allreduce_launches(p2p_reduce_scatter_kernel, p2p_oneshot_kernel, p2p_all_gather_kernel, x, n / 4, one,
+                            make_peer_table(bases, world), rank, world, half_bytes, epoch, err, st, (f32x4*)out,
+                            (const uint32_t*)epoch);
 }
 
 // out (fp32) = resid + bias + sum over ranks of x (bf16, n % 8 == 0, n * 2 <= half_bytes); resid / bias
@@ -776,36 +789,10 @@ int dtc_p2p_allreduce_bf16(const bf16* x, float* out, long n, void* const* bases
                            uint32_t* epoch, int* err, int mode, const float* resid, const float* bias, int ncols,
                            hipStream_t st) {
   if (world < 1 || world > P2P_MAX || n % 8 || n * 2 > half_bytes || (bias && (ncols <= 0 || ncols % 8))) return 4001;
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
-  const long n8 = n / 8;
-  const int blocks = (int)std::min(1024L, std::max(1L, (n8 + 255) / 256));
   const bool one = mode == 2 || (mode == 0 && oneshot_auto(n * 2, world));
-  if (x) {
-    hipLaunchKernelGGL(p2p_stage_bf16_kernel, dim3(blocks), dim3(256), 0, st, (const bf16x8*)x, t, rank, n8,
-                       half_bytes, epoch);
-    DTC_CHECK_LAUNCH();
-  }
-  if (one) {
-    hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
-    DTC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(p2p_oneshot_bf16_kernel, dim3(blocks), dim3(256), 0, st, t, world, n8, half_bytes, out, resid,
-                       bias, ncols, epoch);
-    DTC_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 1);
-  DTC_CHECK_LAUNCH();
-  const int rs_blocks = (int)std::min(1024L, std::max(1L, (n8 / world + 255) / 256));
-  hipLaunchKernelGGL(p2p_reduce_scatter_bf16_kernel, dim3(rs_blocks), dim3(256), 0, st, t, rank, world, n8, half_bytes,
-                     epoch);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 1);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_all_gather_bf16_kernel, dim3(blocks), dim3(256), 0, st, t, world, n8, half_bytes, out, resid,
-                     bias, ncols, epoch);
-  DTC_CHECK_LAUNCH();
-  return 0;
+  return allreduce_launches(p2p_reduce_scatter_bf16_kernel, p2p_oneshot_bf16_kernel, p2p_all_gather_bf16_kernel, x,
+                            n / 8, one, make_peer_table(bases, world), rank, world, half_bytes, epoch, err, st, out,
+                            resid, bias, ncols, (const uint32_t*)epoch);
 }
 
 // ---- sequence-parallel collectives (one barrier each, epoch + 2 per call like the one-shot all-reduce)
@@ -820,26 +807,12 @@ int dtc_p2p_reduce_scatter(const void* x, int bf16, float* out, long n_loc, void
   if (world < 1 || world > P2P_MAX || n_loc % 8 || n_loc * world * esz > half_bytes ||
       (bias && (ncols <= 0 || ncols % 8 || n_loc % ncols)))
     return 4001;
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
-  if (x) {
-    const long n16 = n_loc * world * esz / 16;
-    const int sb = (int)std::min(1024L, std::max(1L, (n16 + 255) / 256));
-    hipLaunchKernelGGL(p2p_stage16_kernel, dim3(sb), dim3(256), 0, st, (const u32x4*)x, t, rank, 0L, n16, half_bytes,
-                       epoch);
-    DTC_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
-  DTC_CHECK_LAUNCH();
-  const long n8 = n_loc / 8;
-  const int blocks = (int)std::min(1024L, std::max(1L, (n8 + 255) / 256));
-  if (bf16)
-    hipLaunchKernelGGL(p2p_rs_kernel<true>, dim3(blocks), dim3(256), 0, st, t, rank, world, n8, half_bytes, out, resid,
-                       bias, ncols, epoch);
-  else
-    hipLaunchKernelGGL(p2p_rs_kernel<false>, dim3(blocks), dim3(256), 0, st, t, rank, world, n8, half_bytes, out,
-                       resid, bias, ncols, epoch);
-  DTC_CHECK_LAUNCH();
+  const PeerTable t = make_peer_table(bases, world);
+  const long n16 = n_loc * world * esz / 16, n8 = n_loc / 8;
+  if (x) P2P_LAUNCH(p2p_stage16_kernel, grid_for(n16), 256, st, (const u32x4*)x, t, rank, 0L, n16, half_bytes, epoch);
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, 2);
+  P2P_LAUNCH_IF(bf16, p2p_rs_kernel, grid_for(n8), st, t, rank, world, n8, half_bytes, out, resid, bias, ncols,
+                  epoch);
   return 0;
 }
 
@@ -848,20 +821,13 @@ int dtc_p2p_reduce_scatter(const void* x, int bf16, float* out, long n_loc, void
 int dtc_p2p_all_gather(const void* x, void* out, long loc_bytes, void* const* bases, int rank, int world,
                        long half_bytes, uint32_t* epoch, int* err, hipStream_t st) {
   if (world < 1 || world > P2P_MAX || loc_bytes % 16 || loc_bytes * world > half_bytes) return 4001;
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
+  const PeerTable t = make_peer_table(bases, world);
   const long n16 = loc_bytes / 16;
-  if (x) {
-    const int sb = (int)std::min(1024L, std::max(1L, (n16 + 255) / 256));
-    hipLaunchKernelGGL(p2p_stage16_kernel, dim3(sb), dim3(256), 0, st, (const u32x4*)x, t, rank, rank * n16, n16,
-                       half_bytes, epoch);
-    DTC_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
-  DTC_CHECK_LAUNCH();
-  const int blocks = (int)std::min(1024L, std::max(1L, (n16 * world + 255) / 256));
-  hipLaunchKernelGGL(p2p_ag_kernel, dim3(blocks), dim3(256), 0, st, t, world, n16, half_bytes, (u32x4*)out, epoch);
-  DTC_CHECK_LAUNCH();
+  if (x)
+    P2P_LAUNCH(p2p_stage16_kernel, grid_for(n16), 256, st, (const u32x4*)x, t, rank, rank * n16, n16, half_bytes,
+               epoch);
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, 2);
+  P2P_LAUNCH(p2p_ag_kernel, grid_for(n16 * world), 256, st, t, world, n16, half_bytes, (u32x4*)out, epoch);
   return 0;
 }
 
@@ -878,15 +844,10 @@ int dtc_pp_send(const void* x, long n, void* own_base, long slot_off, long buf_b
                 const uint32_t* epoch, hipStream_t st) {
   if (!own_base || !peer_base || !epoch || !pp_args_ok(n, slot_off, buf_bytes, flag_idx) || ((uintptr_t)x & 15))
     return 4001;
-  if (x) {
-    const long n16 = n / 16;
-    const int blocks = (int)std::min(1024L, std::max(1L, (n16 + 255) / 256));
-    hipLaunchKernelGGL(pp_stage_kernel, dim3(blocks), dim3(256), 0, st, (const u32x4*)x,
-                       (u32x4*)((unsigned char*)own_base + FLAG_BYTES + slot_off), n16, slot_off, buf_bytes);
-    DTC_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(pp_signal_kernel, dim3(1), dim3(64), 0, st, (uint32_t*)peer_base, flag_idx, epoch);
-  DTC_CHECK_LAUNCH();
+  if (x)
+    P2P_LAUNCH(pp_stage_kernel, grid_for(n / 16), 256, st, (const u32x4*)x,
+               (u32x4*)((unsigned char*)own_base + FLAG_BYTES + slot_off), n / 16, slot_off, buf_bytes);
+  P2P_LAUNCH(pp_signal_kernel, 1, 64, st, (uint32_t*)peer_base, flag_idx, epoch);
   return 0;
 }
 
@@ -898,18 +859,10 @@ int dtc_pp_recv(void* out, void* out_f32, long n, const void* peer_base, long sl
   if (!out || !own_base || !peer_base || !epoch || !err || !pp_args_ok(n, slot_off, buf_bytes, flag_idx) ||
       ((uintptr_t)out & 15) || ((uintptr_t)out_f32 & 15))
     return 4001;
-  hipLaunchKernelGGL(pp_wait_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)own_base, flag_idx, epoch, err);
-  DTC_CHECK_LAUNCH();
-  const long n16 = n / 16;
-  const int blocks = (int)std::min(1024L, std::max(1L, (n16 + 255) / 256));
+  P2P_LAUNCH(pp_wait_kernel, 1, 64, st, (const uint32_t*)own_base, flag_idx, epoch, err);
   const u32x4* slot = (const u32x4*)((const unsigned char*)peer_base + FLAG_BYTES + slot_off);
-  if (out_f32)
-    hipLaunchKernelGGL(pp_pull_kernel<true>, dim3(blocks), dim3(256), 0, st, slot, (u32x4*)out, (u32x4*)out_f32, n16,
-                       slot_off, buf_bytes);
-  else
-    hipLaunchKernelGGL(pp_pull_kernel<false>, dim3(blocks), dim3(256), 0, st, slot, (u32x4*)out, (u32x4*)nullptr, n16,
-                       slot_off, buf_bytes);
-  DTC_CHECK_LAUNCH();
+  P2P_LAUNCH_IF(out_f32 != nullptr, pp_pull_kernel, grid_for(n / 16), st, slot, (u32x4*)out, (u32x4*)out_f32, n / 16,
+                  slot_off, buf_bytes);
   return 0;
 }
 
@@ -917,43 +870,28 @@ int dtc_pp_recv(void* out, void* out_f32, long n, const void* peer_base, long sl
 // sum over ranks, in place.  bf16: the payload travels as bf16 (fp32 sums in rank order, one rounding of the
 // reduced slice); ceil(n / 8) 16-byte pieces must fit the half, else n / 4.  Every grid is at most max_blocks
 // blocks (1 .. 1024).  Epoch + 2 like every other call on the object.
+// What the three bucket calls require of their common arguments (buf: the fp32 bucket, grads or params)
+inline bool dp_args_ok(const float* buf, long n, void* const* bases, int rank, int world, long half_bytes,
+                       const uint32_t* epoch, const int* err, int max_blocks) {
+  return buf && bases && epoch && err && world >= 1 && world <= P2P_MAX && rank >= 0 && rank < world && n > 0 &&
+         n % 4 == 0 && !((uintptr_t)buf & 15) && max_blocks >= 1 && max_blocks <= 1024 && half_bytes > 0 &&
+         half_bytes % 16 == 0;
+}
+inline long dp_pieces(long n, int bf16) { return bf16 ? (n + 7) / 8 : n / 4; }  // 16-byte pieces of the payload
+
 int dtc_dp_allreduce(float* grads, long n, int bf16, void* const* bases, int rank, int world, long half_bytes,
                      uint32_t* epoch, int* err, int max_blocks, hipStream_t st) {
-  if (!grads || !bases || !epoch || !err || world < 1 || world > P2P_MAX || rank < 0 || rank >= world || n <= 0 ||
-      n % 4 || ((uintptr_t)grads & 15) || max_blocks < 1 || max_blocks > 1024 || half_bytes <= 0 || half_bytes % 16)
-    return 4001;
-  const long pieces = bf16 ? (n + 7) / 8 : n / 4;
+  if (!dp_args_ok(grads, n, bases, rank, world, half_bytes, epoch, err, max_blocks)) return 4001;
+  const long pieces = dp_pieces(n, bf16);
   if (pieces > half_bytes / 16) return 4001;
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
+  const PeerTable t = make_peer_table(bases, world);
   const long chunk = (pieces + world - 1) / world;
-  const int blocks = (int)std::min((long)max_blocks, std::max(1L, (pieces + 255) / 256));
-  const int rs_blocks = (int)std::min((long)max_blocks, std::max(1L, (chunk + 255) / 256));
-  if (bf16)
-    hipLaunchKernelGGL(dp_pack_kernel<true>, dim3(blocks), dim3(256), 0, st, grads, t, rank, n, pieces, half_bytes,
-                       epoch);
-  else
-    hipLaunchKernelGGL(dp_pack_kernel<false>, dim3(blocks), dim3(256), 0, st, grads, t, rank, n, pieces, half_bytes,
-                       epoch);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 1);
-  DTC_CHECK_LAUNCH();
-  if (bf16)
-    hipLaunchKernelGGL(dp_reduce_kernel<true>, dim3(rs_blocks), dim3(256), 0, st, t, rank, world, pieces, half_bytes,
-                       epoch);
-  else
-    hipLaunchKernelGGL(dp_reduce_kernel<false>, dim3(rs_blocks), dim3(256), 0, st, t, rank, world, pieces, half_bytes,
-                       epoch);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 1);
-  DTC_CHECK_LAUNCH();
-  if (bf16)
-    hipLaunchKernelGGL(dp_gather_kernel<true>, dim3(blocks), dim3(256), 0, st, t, world, n, pieces, half_bytes, grads,
-                       epoch);
-  else
-    hipLaunchKernelGGL(dp_gather_kernel<false>, dim3(blocks), dim3(256), 0, st, t, world, n, pieces, half_bytes, grads,
-                       epoch);
-  DTC_CHECK_LAUNCH();
+  const int blocks = grid_for(pieces, max_blocks);
+  P2P_LAUNCH_IF(bf16, dp_pack_kernel, blocks, st, grads, t, rank, n, pieces, half_bytes, epoch);
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, 1);
+  P2P_LAUNCH_IF(bf16, dp_reduce_kernel, grid_for(chunk, max_blocks), st, t, rank, world, pieces, half_bytes, epoch);
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, 1);
+  P2P_LAUNCH_IF(bf16, dp_gather_kernel, blocks, st, t, world, n, pieces, half_bytes, grads, epoch);
   return 0;
 }
 
@@ -961,9 +899,7 @@ int dtc_dp_allreduce(float* grads, long n, int bf16, void* const* bases, int ran
 // Blocks (= Σg² partial slots) of the reduce-scatter of an n-element bucket; the same on every rank.
 int dtc_dp_rs_slots(long n, int bf16, int world, int max_blocks) {
   if (n <= 0 || n % 4 || world < 1 || world > P2P_MAX || max_blocks < 1 || max_blocks > 1024) return -1;
-  const long pieces = bf16 ? (n + 7) / 8 : n / 4;
-  const long chunk = (pieces + world - 1) / world;
-  return (int)std::min((long)max_blocks, std::max(1L, (chunk + 255) / 256));
+  return grid_for((dp_pieces(n, bf16) + world - 1) / world, max_blocks);
 }
 
 // grads[own slice] (fp32, in place) = sum over ranks of grads[own slice], where the own slice of the n-element
@@ -972,31 +908,14 @@ int dtc_dp_rs_slots(long n, int bf16, int world, int max_blocks) {
 // (nslots == dtc_dp_rs_slots(...)) = per-block partial sums of squares of the slice (zeros for an empty one).
 int dtc_dp_reduce_scatter(float* grads, long n, int bf16, float* part, int nslots, void* const* bases, int rank,
                           int world, long half_bytes, uint32_t* epoch, int* err, int max_blocks, hipStream_t st) {
-  if (!grads || !part || !bases || !epoch || !err || world < 1 || world > P2P_MAX || rank < 0 || rank >= world ||
-      n <= 0 || n % 4 || ((uintptr_t)grads & 15) || ((uintptr_t)part & 3) || max_blocks < 1 || max_blocks > 1024 ||
-      half_bytes <= 0 || half_bytes % 16)
+  if (!dp_args_ok(grads, n, bases, rank, world, half_bytes, epoch, err, max_blocks) || !part || ((uintptr_t)part & 3))
     return 4001;
-  const long pieces = bf16 ? (n + 7) / 8 : n / 4;
+  const long pieces = dp_pieces(n, bf16);
   if (pieces > half_bytes / 16 || nslots != dtc_dp_rs_slots(n, bf16, world, max_blocks)) return 4001;
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
-  const int blocks = (int)std::min((long)max_blocks, std::max(1L, (pieces + 255) / 256));
-  if (bf16)
-    hipLaunchKernelGGL(dp_pack_kernel<true>, dim3(blocks), dim3(256), 0, st, grads, t, rank, n, pieces, half_bytes,
-                       epoch);
-  else
-    hipLaunchKernelGGL(dp_pack_kernel<false>, dim3(blocks), dim3(256), 0, st, grads, t, rank, n, pieces, half_bytes,
-                       epoch);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
-  DTC_CHECK_LAUNCH();
-  if (bf16)
-    hipLaunchKernelGGL(dp_reduce_shard_kernel<true>, dim3(nslots), dim3(256), 0, st, t, rank, world, n, pieces,
-                       half_bytes, grads, part, epoch);
-  else
-    hipLaunchKernelGGL(dp_reduce_shard_kernel<false>, dim3(nslots), dim3(256), 0, st, t, rank, world, n, pieces,
-                       half_bytes, grads, part, epoch);
-  DTC_CHECK_LAUNCH();
+  const PeerTable t = make_peer_table(bases, world);
+  P2P_LAUNCH_IF(bf16, dp_pack_kernel, grid_for(pieces, max_blocks), st, grads, t, rank, n, pieces, half_bytes, epoch);
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, 2);
+  P2P_LAUNCH_IF(bf16, dp_reduce_shard_kernel, nslots, st, t, rank, world, n, pieces, half_bytes, grads, part, epoch);
   return 0;
 }
 
@@ -1007,27 +926,20 @@ int dtc_dp_reduce_scatter(float* grads, long n, int bf16, float* part, int nslot
 int dtc_dp_param_gather(float* params, bf16* mirror, long n, long n_mirror, int bf16_plan, void* const* bases,
                         int rank, int world, long half_bytes, uint32_t* epoch, int* err, int max_blocks,
                         hipStream_t st) {
-  if (!params || !bases || !epoch || !err || world < 1 || world > P2P_MAX || rank < 0 || rank >= world || n <= 0 ||
-      n % 4 || ((uintptr_t)params & 15) || ((uintptr_t)mirror & 7) || n_mirror < 0 || n_mirror > n || n_mirror % 4 ||
-      (n_mirror > 0 && !mirror) || max_blocks < 1 || max_blocks > 1024 || half_bytes <= 0 || half_bytes % 16)
+  if (!dp_args_ok(params, n, bases, rank, world, half_bytes, epoch, err, max_blocks) || ((uintptr_t)mirror & 7) ||
+      n_mirror < 0 || n_mirror > n || n_mirror % 4 || (n_mirror > 0 && !mirror))
     return 4001;
   const int qpp = bf16_plan ? 2 : 1;
   const long nq = n / 4, pieces = (nq + qpp - 1) / qpp;
   const long chunk = (pieces + world - 1) / world;
   if (std::min(nq, chunk * qpp) > half_bytes / 16) return 4001;  // the largest slice (rank 0's) must fit the half
   const long q_lo = std::min(nq, rank * chunk * qpp), q_hi = std::min(nq, q_lo + chunk * qpp);
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
-  const int pk = (int)std::min((long)max_blocks, std::max(1L, (q_hi - q_lo + 255) / 256));
-  hipLaunchKernelGGL(dp_pack_params_kernel, dim3(pk), dim3(256), 0, st, params, t, rank, q_lo, q_hi, half_bytes,
-                     epoch);
-  DTC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
-  DTC_CHECK_LAUNCH();
-  const int blocks = (int)std::min((long)max_blocks, std::max(1L, (nq + 255) / 256));
-  hipLaunchKernelGGL(dp_gather_params_kernel, dim3(blocks), dim3(256), 0, st, t, rank, world, n, pieces, qpp,
-                     half_bytes, params, mirror, n_mirror, epoch);
-  DTC_CHECK_LAUNCH();
+  const PeerTable t = make_peer_table(bases, world);
+  P2P_LAUNCH(dp_pack_params_kernel, grid_for(q_hi - q_lo, max_blocks), 256, st, params, t, rank, q_lo, q_hi, half_bytes,
+             epoch);
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, t, rank, world, epoch, err, 2);
+  P2P_LAUNCH(dp_gather_params_kernel, grid_for(nq, max_blocks), 256, st, t, rank, world, n, pieces, qpp, half_bytes,
+             params, mirror, n_mirror, epoch);
   return 0;
 }
 
@@ -1046,10 +958,7 @@ int dtc_cu_hog(int blocks, long ticks, int lds_bytes, int* sink, hipStream_t st)
 // on every replay of a captured step.
 int dtc_p2p_barrier_round(void* const* bases, int rank, int world, uint32_t* epoch, int* err, hipStream_t st) {
   if (world < 1 || world > P2P_MAX) return 4001;
-  PeerTable t;
-  for (int p = 0; p < P2P_MAX; ++p) t.base[p] = (unsigned char*)(p < world ? bases[p] : nullptr);
-  hipLaunchKernelGGL(p2p_barrier_kernel, dim3(1), dim3(64), 0, st, t, rank, world, epoch, err, 2);
-  DTC_CHECK_LAUNCH();
+  P2P_LAUNCH(p2p_barrier_kernel, 1, 64, st, make_peer_table(bases, world), rank, world, epoch, err, 2);
   return 0;
 }
 

@@ -43,9 +43,13 @@ class LnSync:
         self.err = torch.zeros(1, dtype=torch.int32, device=device)
         self.M, self.D, self.nsites, self.step = M, D, int(nsites), step
 
+    def describe(self, e: int) -> str:
+        return "fused LayerNorm: a row-statistics wait timed out (outputs were NaN)"
+
     def check(self):
-        if int(self.err.item()) != 0:
-            raise RuntimeError("fused LayerNorm: a row-statistics wait timed out (outputs were NaN)")
+        e = int(self.err.item())
+        if e != 0:
+            raise RuntimeError(self.describe(e))
 
 
 def supported(M: int, D: int, K: int) -> bool:

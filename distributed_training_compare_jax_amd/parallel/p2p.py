@@ -75,48 +75,92 @@ def check_peer_access(L, rank: int, dev: int, peers, what: str = "P2P all-reduce
     return out
 
 
-class P2PAllReduce:
-    def __init__(self, group, rank: int, world: int, device, max_bytes: int):
-        assert 1 <= world <= 8, "P2P all-reduce supports up to 8 ranks (one xGMI hive)"
-        self.rank, self.world = rank, world
+# error-word bases of the bounded waits in csrc/p2p.hip (ERR_BARRIER / ERR_FLAG / ERR_PP): a barrier's word is
+# BARRIER_ERR + the rank waited for, a stream flag's FLAG_ERR + its index, a stage message's PP_ERR + its flag word
+BARRIER_ERR, FLAG_ERR, PP_ERR = 1000, 2000, 3000
+
+
+def barrier_timeout_message(label: str, unit: str, rank: int, e: int) -> str:
+    """What a barrier's error word ``e`` says: ``label`` names the transport ("P2P all-reduce (PP group)"),
+    ``unit`` what its members are called ("rank" or "stage"), ``rank`` is this member."""
+    return f"{label}: {unit} {rank} timed out waiting for {unit} {e - BARRIER_ERR}"
+
+
+class PeerBuffer:
+    """This rank's uncached device buffer (flag area + ``nbytes`` of payload), exported over IPC, and the mapped
+    buffers of its ``peers`` (default: every other rank of ``group``); the device epoch counter and error word of
+    the kernels that use them.  One ``all_gather_object`` carries the handles, the PCI bus ids and, if given, a
+    ``plan`` hash every rank must share (``plan_name``: what it hashes, for the message); one barrier ends the
+    init.  ``label`` / ``unit`` / ``alt``: the transport's name in messages, "rank" or "stage", and the setting to
+    recommend when a peer GPU cannot be reached."""
+
+    def __init__(self, group, rank: int, world: int, device, nbytes: int, label: str, unit: str, alt: str,
+                 peers=None, plan: str = None, plan_name: str = ""):
+        self.rank, self.world, self.label, self.unit = rank, world, label, unit
         self.device = torch.device(device)
-        self.half = (int(max_bytes) + 4095) // 4096 * 4096
         L = N.lib()
-        total = int(L.dtc_p2p_flag_bytes()) + 2 * self.half
+        self._flag_bytes = int(L.dtc_p2p_flag_bytes())
         ptr = ctypes.c_void_p()
         handle = ctypes.create_string_buffer(64)
         with torch.cuda.device(self.device):
-            N.check(L.dtc_p2p_alloc(total, ctypes.addressof(ptr), ctypes.addressof(handle)), "dtc_p2p_alloc")
+            N.check(L.dtc_p2p_alloc(self._flag_bytes + int(nbytes), ctypes.addressof(ptr), ctypes.addressof(handle)),
+                    "dtc_p2p_alloc")
         self._own = ptr.value
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
         info = [None] * world
-        dist.all_gather_object(info, (bytes(handle.raw), _pci_bus_id(L, dev)), group=group)
-        self.peer_paths = check_peer_access(L, rank, dev, [(p, bus) for p, (_, bus) in enumerate(info)])
-        bases = []
-        self._opened = []
+        mine = (bytes(handle.raw), _pci_bus_id(L, dev)) + (() if plan is None else (plan,))
+        dist.all_gather_object(info, mine, group=group)
+        for p, other in enumerate(info):
+            if plan is not None and other[2] != plan:
+                raise RuntimeError(f"{label}: {unit} {rank} and {unit} {p} derived different {plan_name} "
+                                   f"({plan[:12]} vs {other[2][:12]}): their configurations differ")
+        peers = [p for p in (range(world) if peers is None else peers) if p != rank]
+        self.peer_paths = check_peer_access(L, rank, dev, [(p, info[p][1]) for p in peers], what=label, alt=alt)
+        self._mapped = {}  # peer -> its buffer's base as mapped here
         with torch.cuda.device(self.device):
-            for p, (h, bus) in enumerate(info):
-                if p == rank:
-                    bases.append(self._own)
-                    continue
+            for p in peers:
                 q = ctypes.c_void_p()
-                hb = ctypes.create_string_buffer(h, 64)
+                hb = ctypes.create_string_buffer(info[p][0], 64)
                 rc = L.dtc_p2p_open(ctypes.addressof(hb), ctypes.addressof(q))
                 if rc != 0:
-                    raise RuntimeError(f"P2P all-reduce: rank {rank} could not map rank {p}'s buffer (GPU {bus}): "
+                    raise RuntimeError(f"{label}: {unit} {rank} could not map {unit} {p}'s buffer (GPU {info[p][1]}): "
                                        f"hipIpcOpenMemHandle error {rc}")
-                bases.append(q.value)
-                self._opened.append(q.value)
-        self._bases = (ctypes.c_void_p * 8)(*(bases + [None] * (8 - world)))
-        self._bases_ptr = ctypes.addressof(self._bases)
+                self._mapped[p] = q.value
         self.epoch = torch.zeros(1, dtype=torch.int32, device=self.device)
-        # calls issued so far (host mirror of epoch / 2): the buffer half of the next call is calls & 1
-        self.calls = 0
-        self._flag_bytes = int(L.dtc_p2p_flag_bytes())
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
-        # all ranks' flag areas are zero before anyone's first barrier can run
+        # all ranks' flag areas are zero before anyone's first barrier or signal can run
         torch.cuda.synchronize(self.device)
         dist.barrier(group=group)
+
+    def close(self):
+        L = N.lib()
+        for q in self._mapped.values():
+            L.dtc_p2p_close(ctypes.c_void_p(q))
+        self._mapped = {}
+        if self._own:
+            L.dtc_p2p_free(ctypes.c_void_p(self._own))
+            self._own = None
+
+
+class P2PAllReduce(PeerBuffer):
+    def __init__(self, group, rank: int, world: int, device, max_bytes: int, label: str = "P2P all-reduce",
+                 unit: str = "rank"):
+        assert 1 <= world <= 8, "P2P all-reduce supports up to 8 ranks (one xGMI hive)"
+        self.half = (int(max_bytes) + 4095) // 4096 * 4096
+        super().__init__(group, rank, world, device, 2 * self.half, "P2P all-reduce", "rank", "tp_comm: rccl")
+        self.label, self.unit = label, unit  # (of describe(); init and check() speak of "P2P all-reduce" ranks)
+        bases = [self._own if p == rank else self._mapped[p] for p in range(world)]
+        self._bases = (ctypes.c_void_p * 8)(*(bases + [None] * (8 - world)))
+        self._bases_ptr = ctypes.addressof(self._bases)
+        # what every native call on the object takes, in this order
+        self._targs = (self._bases_ptr, rank, world, self.half, self.epoch.data_ptr(), self.err.data_ptr())
+        # calls issued so far (host mirror of epoch / 2): the buffer half of the next call is calls & 1
+        self.calls = 0
+
+    def _call(self, name: str, head, *tail):
+        """``name(*head, <bases, rank, world, half, epoch, err>, *tail)``, checked; one more call on the object."""
+        N.check(getattr(N.lib(), name)(*head, *self._targs, *tail), name)
+        self.calls += 1
 
     def supports(self, t: torch.Tensor) -> bool:
         return (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() % 4 == 0
@@ -126,10 +170,7 @@ class P2PAllReduce:
         """In-place sum over the group.  mode 0: one-shot (one barrier, every rank reads every peer) at
         W = 2 and for small messages (<= 1 MiB at W <= 4, <= 512 KiB at W >= 5), else two-shot (reduce-scatter
         + all-gather, 2 (W-1)/W of the bytes per rank); 1 / 2 force two-shot / one-shot."""
-        N.check(N.lib().dtc_p2p_allreduce(t.data_ptr(), t.data_ptr(), t.numel(), self._bases_ptr, self.rank, self.world,
-                                          self.half, self.epoch.data_ptr(), self.err.data_ptr(), int(mode),
-                                          N.stream_ptr(t.device)), "dtc_p2p_allreduce")
-        self.calls += 1
+        self._call("dtc_p2p_allreduce", (t.data_ptr(), t.data_ptr(), t.numel()), int(mode), N.stream_ptr(t.device))
         return t
 
     def staged_out(self, numel: int, dtype=torch.bfloat16):
@@ -147,9 +188,8 @@ class P2PAllReduce:
     def end_step(self):
         """Pad the step's calls to an even count with a payload-free barrier round (epoch + 2)."""
         if self.calls & 1:
-            N.check(N.lib().dtc_p2p_barrier_round(self._bases_ptr, self.rank, self.world, self.epoch.data_ptr(),
-                                                  self.err.data_ptr(), N.stream_ptr(self.device)),
-                    "dtc_p2p_barrier_round")
+            N.check(N.lib().dtc_p2p_barrier_round(*self._targs[:3], *self._targs[4:], N.stream_ptr(self.device)),
+                    "dtc_p2p_barrier_round")  # (the one call that takes no half)
             self.calls += 1
 
     def supports_bf16(self, x: torch.Tensor) -> bool:
@@ -164,11 +204,8 @@ class P2PAllReduce:
         ncols = out.shape[-1] if bias is not None else 0
         n = out.numel() if x is None else x.numel()
         assert x is not None or n * 2 <= self.half
-        N.check(N.lib().dtc_p2p_allreduce_bf16(N.ptr(x), out.data_ptr(), n, self._bases_ptr, self.rank,
-                                               self.world, self.half, self.epoch.data_ptr(), self.err.data_ptr(),
-                                               int(mode), N.ptr(resid), N.ptr(bias), ncols, N.stream_ptr(out.device)),
-                "dtc_p2p_allreduce_bf16")
-        self.calls += 1
+        self._call("dtc_p2p_allreduce_bf16", (N.ptr(x), out.data_ptr(), n), int(mode), N.ptr(resid), N.ptr(bias), ncols,
+                   N.stream_ptr(out.device))
         return out
 
     # ---- sequence parallelism: row-sharded residual stream (parallel/tp.py TPComm.*_rows)
@@ -183,12 +220,8 @@ class P2PAllReduce:
         if rows % self.world:  # rows // W would drop the last rows and shift every rank's slice
             raise RuntimeError(f"P2P reduce-scatter: {rows} rows do not divide over {self.world} ranks")
         n_loc = rows // self.world * cols
-        N.check(N.lib().dtc_p2p_reduce_scatter(N.ptr(x), int(dtype == torch.bfloat16), out.data_ptr(), n_loc,
-                                               self._bases_ptr, self.rank, self.world, self.half,
-                                               self.epoch.data_ptr(), self.err.data_ptr(), N.ptr(resid), N.ptr(bias),
-                                               cols if bias is not None else 0, N.stream_ptr(out.device)),
-                "dtc_p2p_reduce_scatter")
-        self.calls += 1
+        self._call("dtc_p2p_reduce_scatter", (N.ptr(x), int(dtype == torch.bfloat16), out.data_ptr(), n_loc),
+                   N.ptr(resid), N.ptr(bias), cols if bias is not None else 0, N.stream_ptr(out.device))
         return out
 
     def supports_ag(self, x: torch.Tensor) -> bool:
@@ -197,10 +230,8 @@ class P2PAllReduce:
 
     def all_gather(self, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """out [W * rows, ...] (rank-major) = every rank's ``x`` (any dtype, 16-byte multiple)."""
-        N.check(N.lib().dtc_p2p_all_gather(x.data_ptr(), out.data_ptr(), x.numel() * x.element_size(),
-                                           self._bases_ptr, self.rank, self.world, self.half, self.epoch.data_ptr(),
-                                           self.err.data_ptr(), N.stream_ptr(out.device)), "dtc_p2p_all_gather")
-        self.calls += 1
+        self._call("dtc_p2p_all_gather", (x.data_ptr(), out.data_ptr(), x.numel() * x.element_size()),
+                   N.stream_ptr(out.device))
         return out
 
     def check(self):
@@ -220,21 +251,16 @@ class P2PAllReduce:
         are then one half off on replay.  Always pad out-of-step use with :meth:`end_step`."""
         e = int(self.err.item())
         if e:
-            raise RuntimeError(f"P2P all-reduce: rank {self.rank} timed out waiting for rank {e - 1000}")
+            raise RuntimeError(barrier_timeout_message("P2P all-reduce", "rank", self.rank, e))
         dev_half = (int(self.epoch.item()) >> 1) & 1
         if dev_half != (self.calls & 1):
             raise RuntimeError(f"P2P all-reduce: rank {self.rank} buffer-half mismatch (device epoch "
                                f"{int(self.epoch.item())}, host calls {self.calls}): a captured graph with an odd "
                                "number of P2P calls was replayed; end every captured step with end_step()")
 
-    def close(self):
-        L = N.lib()
-        for q in self._opened:
-            L.dtc_p2p_close(ctypes.c_void_p(q))
-        self._opened = []
-        if self._own:
-            L.dtc_p2p_free(ctypes.c_void_p(self._own))
-            self._own = None
+    def describe(self, e: int) -> str:
+        """The message for this object's error word ``e`` under its ``label`` (which group) and ``unit``."""
+        return barrier_timeout_message(self.label, self.unit, self.rank, e)
 
 
 # ------------------------------------------------------------------------------ DP gradient buckets
@@ -295,7 +321,7 @@ class P2PGradReduce(P2PAllReduce):
             if h != self.plan_hash:
                 raise RuntimeError(f"P2P grad reduce: rank {rank} and rank {p} derived different bucket plans "
                                    f"({self.plan_hash[:12]} vs {h[:12]}): their configurations differ")
-        super().__init__(group, rank, world, device, half)
+        super().__init__(group, rank, world, device, half, label="P2P all-reduce (DP group)")
         assert self.half == half
         if max_blocks is None:
             max_blocks = int(os.environ.get("DTC_DP_P2P_BLOCKS", str(DP_P2P_BLOCKS)))
@@ -312,18 +338,21 @@ class P2PGradReduce(P2PAllReduce):
         half = dp_half_bytes(self.buckets, self.payload, self.gather_bytes)
         return half, dp_plan_hash(world, self.buckets, self.payload, half, self.gather_bytes)
 
+    def _bf(self, bf16) -> int:
+        """The ``bf16`` argument of a bucket call: the object's payload unless the caller says otherwise."""
+        return int(self.payload == "bf16" if bf16 is None else bool(bf16))
+
+    def _blocks(self, max_blocks) -> int:
+        return self.max_blocks if max_blocks is None else int(max_blocks)
+
     def bucket_all_reduce_(self, t: torch.Tensor, bf16: bool = None, max_blocks: int = None) -> torch.Tensor:
         """In-place sum of a slice of the flat fp32 grads over the group (``dtc_dp_allreduce``: pack, barrier,
         rank-order reduce of this rank's slice, barrier, gather; grids capped at ``max_blocks``)."""
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
             raise RuntimeError(f"P2P grad reduce: rank {self.rank} bucket is {tuple(t.shape)} {t.dtype} on {t.device}; "
                                "needs a contiguous fp32 GPU tensor")
-        bf = (self.payload == "bf16") if bf16 is None else bool(bf16)
-        N.check(N.lib().dtc_dp_allreduce(t.data_ptr(), t.numel(), int(bf), self._bases_ptr, self.rank, self.world,
-                                         self.half, self.epoch.data_ptr(), self.err.data_ptr(),
-                                         self.max_blocks if max_blocks is None else int(max_blocks),
-                                         N.stream_ptr(t.device)), "dtc_dp_allreduce")
-        self.calls += 1
+        self._call("dtc_dp_allreduce", (t.data_ptr(), t.numel(), self._bf(bf16)), self._blocks(max_blocks),
+                   N.stream_ptr(t.device))
         return t
 
     def on_comm(self, fn, keep=(), mark: bool = False):
@@ -448,9 +477,7 @@ class P2PZeroShard(P2PGradReduce):
         return half, zero_plan_hash(world, self.buckets, self.payload, half)
 
     def rs_slots(self, numel: int, bf16: bool = None, max_blocks: int = None) -> int:
-        bf = (self.payload == "bf16") if bf16 is None else bool(bf16)
-        return dp_rs_slots(numel, "bf16" if bf else "fp32", self.world,
-                           self.max_blocks if max_blocks is None else int(max_blocks))
+        return dp_rs_slots(numel, "bf16" if self._bf(bf16) else "fp32", self.world, self._blocks(max_blocks))
 
     def bucket_reduce_scatter_(self, t: torch.Tensor, part: torch.Tensor, bf16: bool = None,
                                max_blocks: int = None) -> torch.Tensor:
@@ -461,13 +488,8 @@ class P2PZeroShard(P2PGradReduce):
                 and part.dtype == torch.float32 and part.is_contiguous()):
             raise RuntimeError(f"P2P zero shard: rank {self.rank} bucket is {tuple(t.shape)} {t.dtype} on {t.device}; "
                                "needs contiguous fp32 GPU tensors")
-        bf = (self.payload == "bf16") if bf16 is None else bool(bf16)
-        N.check(N.lib().dtc_dp_reduce_scatter(t.data_ptr(), t.numel(), int(bf), part.data_ptr(), part.numel(),
-                                              self._bases_ptr, self.rank, self.world, self.half,
-                                              self.epoch.data_ptr(), self.err.data_ptr(),
-                                              self.max_blocks if max_blocks is None else int(max_blocks),
-                                              N.stream_ptr(t.device)), "dtc_dp_reduce_scatter")
-        self.calls += 1
+        self._call("dtc_dp_reduce_scatter", (t.data_ptr(), t.numel(), self._bf(bf16), part.data_ptr(), part.numel()),
+                   self._blocks(max_blocks), N.stream_ptr(t.device))
         return t
 
     def bucket_param_gather_(self, p: torch.Tensor, mirror=None, n_mirror: int = 0, bf16: bool = None,
@@ -483,12 +505,8 @@ class P2PZeroShard(P2PGradReduce):
                              and mirror.numel() >= n_mirror):
             raise RuntimeError(f"P2P zero shard: rank {self.rank} mirror of {n_mirror} elements needs a contiguous "
                                "bf16 tensor at least that long")
-        bf = (self.payload == "bf16") if bf16 is None else bool(bf16)
-        N.check(N.lib().dtc_dp_param_gather(p.data_ptr(), N.ptr(mirror) if n_mirror else None, p.numel(),
-                                            int(n_mirror), int(bf), self._bases_ptr, self.rank, self.world, self.half,
-                                            self.epoch.data_ptr(), self.err.data_ptr(), int(max_blocks),
-                                            N.stream_ptr(p.device)), "dtc_dp_param_gather")
-        self.calls += 1
+        self._call("dtc_dp_param_gather", (p.data_ptr(), N.ptr(mirror) if n_mirror else None, p.numel(), int(n_mirror),
+                                           self._bf(bf16)), int(max_blocks), N.stream_ptr(p.device))
         return p
 
 
@@ -592,7 +610,7 @@ def pp_table_hash(S: int, M: int, head_split: bool, table) -> str:
     return hashlib.sha256(repr((S, M, bool(head_split), rows, [t["bytes"] for t in table])).encode()).hexdigest()
 
 
-class P2PPipe:
+class P2PPipe(PeerBuffer):
     """The pipeline stage messages of one PP group as in-graph kernels (``TrainConfig.pp_comm: p2p``).
 
     ``send`` / ``recv`` enqueue kernels on the current stream and return at once: nothing here calls the process
@@ -605,49 +623,16 @@ class P2PPipe:
     def __init__(self, group, stage: int, n_stages: int, device, n_micro: int, head_split: bool, msgs):
         if not 2 <= n_stages <= 8:
             raise ValueError(f"P2P pipe: {n_stages} stages; supports 2 to 8 (one xGMI hive)")
-        self.rank, self.world = stage, n_stages
-        self.device = torch.device(device)
         full = pp_slot_table(n_stages, n_micro, head_split, msgs)
         self.table = full[stage]
         self._hash = pp_table_hash(n_stages, n_micro, head_split, full)
-        L = N.lib()
-        self._flag_bytes = int(L.dtc_p2p_flag_bytes())
-        assert self._flag_bytes == 4 * FLAG_WORDS
         self.bytes = self.table["bytes"]
-        ptr = ctypes.c_void_p()
-        handle = ctypes.create_string_buffer(64)
-        with torch.cuda.device(self.device):
-            N.check(L.dtc_p2p_alloc(self._flag_bytes + max(self.bytes, 4096), ctypes.addressof(ptr),
-                                    ctypes.addressof(handle)), "dtc_p2p_alloc")
-        self._own = ptr.value
-        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        info = [None] * n_stages
-        dist.all_gather_object(info, (bytes(handle.raw), _pci_bus_id(L, dev), self._hash), group=group)
-        for p, (_, _, h) in enumerate(info):
-            if h != self._hash:
-                raise RuntimeError(f"P2P pipe: stage {stage} and stage {p} derived different slot tables "
-                                   f"({self._hash[:12]} vs {h[:12]}): their configurations differ")
         near = [p for p in (stage - 1, stage + 1) if 0 <= p < n_stages]
-        self.peer_paths = check_peer_access(L, stage, dev, [(p, info[p][1]) for p in near], what="P2P pipe",
-                                            alt="pp_comm: rccl")
-        self._peer = {}
-        self._opened = []
-        with torch.cuda.device(self.device):
-            for p in near:
-                q = ctypes.c_void_p()
-                hb = ctypes.create_string_buffer(info[p][0], 64)
-                rc = L.dtc_p2p_open(ctypes.addressof(hb), ctypes.addressof(q))
-                if rc != 0:
-                    raise RuntimeError(f"P2P pipe: stage {stage} could not map stage {p}'s buffer (GPU {info[p][1]}): "
-                                       f"hipIpcOpenMemHandle error {rc}")
-                self._peer[p - stage] = q.value
-                self._opened.append(q.value)
-        self.epoch = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        super().__init__(group, stage, n_stages, device, max(self.bytes, 4096), "P2P pipe", "stage", "pp_comm: rccl",
+                         peers=near, plan=self._hash, plan_name="slot tables")
+        assert self._flag_bytes == 4 * FLAG_WORDS
+        self._peer = {p - stage: q for p, q in self._mapped.items()}  # +1 / -1 -> the neighbour's buffer
         self._flag_names = {v.flag: (k, v.peer) for k, v in self.table["recv"].items()}
-        # all stages' flag areas are zero before anyone's first signal can land
-        torch.cuda.synchronize(self.device)
-        dist.barrier(group=group)
 
     def begin_step(self):
         """Bump the step epoch; once per step, inside the step (so a replayed graph bumps it too)."""
@@ -692,8 +677,8 @@ class P2PPipe:
                                     N.stream_ptr(self.device)), "dtc_pp_recv")
 
     def describe(self, e: int) -> str:
-        (tag, i), peer = self._flag_names.get(e - 3000, (("?", -1), 0))
-        return (f"P2P pipe: stage {self.rank} timed out waiting for flag {e - 3000} (message ({tag!r}, {i}) from "
+        (tag, i), peer = self._flag_names.get(e - PP_ERR, (("?", -1), 0))
+        return (f"P2P pipe: stage {self.rank} timed out waiting for flag {e - PP_ERR} (message ({tag!r}, {i}) from "
                 f"stage {self.rank + peer})")
 
     def check(self):
@@ -701,12 +686,3 @@ class P2PPipe:
         e = int(self.err.item())
         if e:
             raise RuntimeError(self.describe(e))
-
-    def close(self):
-        L = N.lib()
-        for q in self._opened:
-            L.dtc_p2p_close(ctypes.c_void_p(q))
-        self._opened = []
-        if self._own:
-            L.dtc_p2p_free(ctypes.c_void_p(self._own))
-            self._own = None

@@ -235,6 +235,9 @@ class Engine:
         # so no copy-back from gloo's worker thread can queue behind a later cross-process wait
         # (parallel/dist.py explains the ordering argument)
         self.program.sync_comms = bool(on_gpu and dinfo.backend == "gloo" and (dinfo.world > 1 or self.dp_comm))
+        # every object with a device error word, in the order of the words loss_handle copies: filled by _register
+        # where each is created; close, check_health, _err_words and read_loss go through it
+        self._transports = {name: None for name in ("p2p", "pp_pipe", "pp_ar", "dp_p2p", "ln")}
         self.p2p = None
         self.pp_pipe = None  # pp_comm: p2p -- the stage messages (created with the message buffers below)
         self.pp_ar = None    # ... and the PP group's scalar sums (loss, pp_clip: global norm)
@@ -244,7 +247,8 @@ class Engine:
             from ..parallel.p2p import P2PAllReduce
 
             rows = self.mb_rows if pp > 1 else self.b_local
-            self.p2p = P2PAllReduce(m.tp_group, m.tp_idx, tp, self.device, rows * T * model_cfg.d_model * 4)
+            self.p2p = self._register("p2p", P2PAllReduce(m.tp_group, m.tp_idx, tp, self.device,
+                                                          rows * T * model_cfg.d_model * 4))
         self.tp_comm = TPComm(m.tp_group, tp, m.tp_idx, self.program, p2p=self.p2p)
         self.stage = GPTStage(model_cfg, self.flat, self.layout, self.tp_comm, dropout_seed=train_cfg.seed,
                               act_dtype=self.act_dtype)
@@ -463,8 +467,9 @@ class Engine:
         if (lnf and on_gpu and self.act_dtype == torch.bfloat16 and tp == 1 and pp == 1 and not self.dp_comm
                 and not self.defer_opt and self.grad_accum == 1):
             has_wt = len(self.layout.layers) > 0 and self.flat.wt(f"h.{self.layout.layers[0]}.fc1.w") is not None
-            self.stage.enable_ln_fusion(self.b_local * T, self.opt.step_t, fwd=bool(lnf & 1),
-                                        bwd=bool(lnf & 2) and has_wt)
+            if self.stage.enable_ln_fusion(self.b_local * T, self.opt.step_t, fwd=bool(lnf & 1),
+                                           bwd=bool(lnf & 2) and has_wt):
+                self._register("ln", self.stage.ln_sync)
         if train_cfg.fwd_gemm_dtype == "fp8":
             self.stage.enable_fp8_forward()
         elif train_cfg.fwd_gemm_dtype == "mxfp8":
@@ -494,8 +499,10 @@ class Engine:
         if self.pp_head_split:
             msgs["fh"] = (n, self.act_dtype)
             msgs["s"] = (self.mb_rows * self.T * 3, torch.float32)
-        self.pp_pipe = P2PPipe(m.pp_group, m.pp_idx, pp, self.device, self.n_micro, self.pp_head_split, msgs)
-        self.pp_ar = P2PAllReduce(m.pp_group, m.pp_idx, pp, self.device, 4096)
+        self.pp_pipe = self._register("pp_pipe", P2PPipe(m.pp_group, m.pp_idx, pp, self.device, self.n_micro,
+                                                         self.pp_head_split, msgs))
+        self.pp_ar = self._register("pp_ar", P2PAllReduce(m.pp_group, m.pp_idx, pp, self.device, 4096,
+                                                          label="P2P all-reduce (PP group)", unit="stage"))
         self.pp_sum = TPComm(m.pp_group, pp, m.pp_idx, self.program, p2p=self.pp_ar)
         self.opt.pp_comm = self.pp_sum
 
@@ -511,13 +518,8 @@ class Engine:
         if self.embed_gather:
             gather = (self.dh_all_bf if self.dh_all_bf is not None else self.dh_all).numel() * \
                 (2 if self.dh_all_bf is not None else 4)
-        self.dp_p2p = P2PGradReduce(m.dp_group, m.dp_idx, m.dp, self.device, self.buckets.buckets,
-                                    self.buckets.payload, gather)
-        self.buckets.peer = self.dp_p2p
-        self._loss4 = torch.zeros(4, dtype=torch.float32, device=self.device)
-        self.loss = self._loss4[:1]
-        self._gather_ev = None
-        self.program.before_comm.append(self._join_dp_p2p)
+        self._attach_dp_p2p(P2PGradReduce(m.dp_group, m.dp_idx, m.dp, self.device, self.buckets.buckets,
+                                          self.buckets.payload, gather))
 
     def _init_zero_p2p(self):
         """``zero_comm: p2p``: one :class:`parallel.p2p.P2PZeroShard` on the DP group, sized for the larger of a
@@ -527,15 +529,27 @@ class Engine:
         from ..parallel.p2p import P2PZeroShard
 
         m = self.mesh
-        self.dp_p2p = P2PZeroShard(m.dp_group, m.dp_idx, m.dp, self.device, self.buckets.buckets,
-                                   self.buckets.payload)
-        self.opt.attach(self.dp_p2p)
-        self.buckets.peer = self.dp_p2p
+        peer = P2PZeroShard(m.dp_group, m.dp_idx, m.dp, self.device, self.buckets.buckets, self.buckets.payload)
+        self.opt.attach(peer)
         self.buckets.scatter_parts = self.opt.parts
+        self._attach_dp_p2p(peer)
+
+    def _attach_dp_p2p(self, peer):
+        """What ``dp_comm: p2p`` and ``zero_comm: p2p`` do alike with their peer object: it carries the buckets, the
+        loss becomes the first of the 4 floats its sum kernel moves, and the join hook ends every capture."""
+        self.dp_p2p = self._register("dp_p2p", peer)
+        self.buckets.peer = peer
         self._loss4 = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.loss = self._loss4[:1]
         self._gather_ev = None
         self.program.before_comm.append(self._join_dp_p2p)
+
+    def _register(self, name: str, transport):
+        self._transports[name] = transport
+        return transport
+
+    def _live_transports(self):
+        return [(name, t) for name, t in self._transports.items() if t is not None]
 
     def _join_dp_p2p(self):
         if self.dp_p2p is not None:
@@ -543,10 +557,10 @@ class Engine:
 
     def close(self):
         """Release the peer-to-peer transports (IPC mappings and their uncached buffers)."""
-        for name in ("pp_pipe", "pp_ar", "p2p", "dp_p2p"):
-            t = getattr(self, name, None)
-            if t is not None:
+        for name, t in self._live_transports():
+            if name != "ln":  # (the fused LayerNorms' granule buffer is an ordinary tensor)
                 t.close()
+                self._transports[name] = None
                 setattr(self, name, None)
 
     def _wgrad_group_for_memory(self, mc: ModelConfig, n_layers: int) -> int:
@@ -1023,31 +1037,14 @@ class Engine:
     def check_health(self):
         """Raise if a device-side wait of this rank timed out (P2P all-reduce flags, fused LayerNorm
         row statistics).  Blocking: call outside pipelined loops."""
-        if self.p2p is not None:
-            self.p2p.check()
-        if self.pp_pipe is not None:
-            self.pp_pipe.check()
-            self.pp_ar.check()
-        if self.dp_p2p is not None:
-            self.dp_p2p.check()
-        if self.stage.ln_sync is not None:
-            self.stage.ln_sync.check()
+        for _, t in self._live_transports():
+            t.check()
 
     # -- host pipelining: read step t's loss while step t+1 is already queued --------------
     def _err_words(self):
         """Device error words of this rank's in-launch waits (P2P all-reduce flags, fused LayerNorm
         row statistics): nonzero = a wait timed out and that step computed NaN."""
-        out = []
-        if self.p2p is not None:
-            out.append(("p2p", self.p2p.err))
-        if self.pp_pipe is not None:
-            out.append(("pp_pipe", self.pp_pipe.err))
-            out.append(("pp_ar", self.pp_ar.err))
-        if self.dp_p2p is not None:
-            out.append(("dp_p2p", self.dp_p2p.err))
-        if self.stage.ln_sync is not None:
-            out.append(("ln", self.stage.ln_sync.err))
-        return out
+        return [(name, t.err) for name, t in self._live_transports()]
 
     def loss_handle(self):
         """Queue a copy of this step's loss (and of the error words) to pinned host memory (2-slot
@@ -1079,20 +1076,10 @@ class Engine:
             return handle
         slot, ev, eslot = handle
         ev.synchronize()
-        for j, (name, _) in enumerate(self._err_words()):
+        for j, (_, t) in enumerate(self._live_transports()):
             e = int(eslot[j])
             if e:
-                if name == "p2p":
-                    raise RuntimeError(f"P2P all-reduce: rank {self.p2p.rank} timed out waiting for rank {e - 1000}")
-                if name == "pp_pipe":
-                    raise RuntimeError(self.pp_pipe.describe(e))
-                if name == "pp_ar":
-                    raise RuntimeError(f"P2P all-reduce (PP group): stage {self.pp_ar.rank} timed out waiting for "
-                                       f"stage {e - 1000}")
-                if name == "dp_p2p":
-                    raise RuntimeError(f"P2P all-reduce (DP group): rank {self.dp_p2p.rank} timed out waiting for "
-                                       f"rank {e - 1000}")
-                raise RuntimeError("fused LayerNorm: a row-statistics wait timed out (outputs were NaN)")
+                raise RuntimeError(t.describe(e))
         return float(slot.item()) / self.mesh.dp
 
     def grad_norm(self) -> float:

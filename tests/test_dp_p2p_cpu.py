@@ -195,3 +195,25 @@ def test_selfcheck_slice_bounds(W):
         covered = [i for lo, hi in b for i in range(lo, hi)]
         assert covered == list(range(pieces))
     assert slice_bounds(1, W, W - 1) == (1, 1)  # 4 elements in bf16 mode: one piece, every other rank owns nothing
+
+
+# ------------------------------------------------------------------------------------------------ timeout messages
+
+def test_barrier_timeout_messages_and_error_bases():
+    """The pure decoder of a barrier's error word gives the three all-reduce messages the engine raises, and the
+    error bases are the ones the kernels store (csrc/p2p.hip)."""
+    import os
+    import re
+
+    from distributed_training_compare_jax_amd.parallel import p2p
+
+    assert (p2p.BARRIER_ERR, p2p.FLAG_ERR, p2p.PP_ERR) == (1000, 2000, 3000)
+    msg = p2p.barrier_timeout_message
+    assert msg("P2P all-reduce", "rank", 1, 1003) == "P2P all-reduce: rank 1 timed out waiting for rank 3"
+    assert msg("P2P all-reduce (PP group)", "stage", 0, 1001) == \
+        "P2P all-reduce (PP group): stage 0 timed out waiting for stage 1"
+    assert msg("P2P all-reduce (DP group)", "rank", 7, 1000) == \
+        "P2P all-reduce (DP group): rank 7 timed out waiting for rank 0"
+    src = open(os.path.join(os.path.dirname(p2p.__file__), "..", "csrc", "p2p.hip")).read()
+    dev = re.search(r"ERR_BARRIER = (\d+), ERR_FLAG = (\d+), ERR_PP = (\d+);", src)
+    assert dev and tuple(map(int, dev.groups())) == (1000, 2000, 3000)

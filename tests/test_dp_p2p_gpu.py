@@ -58,7 +58,8 @@ def inputs(key, n, world):
 
 
 # ------------------------------------------------------------------------------------------------ emulations
-# (csrc/p2p.hip, "DP gradient buckets": dp_pack_kernel / dp_reduce_kernel / dp_gather_kernel)
+# (csrc/p2p.hip, "DP gradient buckets": dp_pack_kernel / dp_reduce_kernel (rank_sum_f32, rank_sum_bf16) /
+# dp_gather_kernel (widen_bf16x8))
 
 def emu_bucket(xs, bf16):
     """What every rank holds after the call, fp32 [n]."""

@@ -86,7 +86,8 @@ def _bits(key, rank, n):
 
 
 # ------------------------------------------------------------------------------------------------ emulations
-# (csrc/p2p.hip: p2p_reduce_scatter_kernel / p2p_oneshot_kernel; add8 + finish8; p2p_rs_kernel; p2p_ag_kernel)
+# (csrc/p2p.hip: rank_sum_f32 in p2p_reduce_scatter_kernel / p2p_oneshot_kernel; rank_sum_bf16 + finish8;
+# p2p_rs_kernel; p2p_ag_kernel)
 
 def emu_sum_f32(xs):
     """fp32 all-reduce, either mode: s = x[0]; s = s + x[p] in rank order."""
