@@ -59,6 +59,14 @@ are optional and default to the reference behaviour:
   (N, warmup included) and ``lr_min_ratio`` (r): ``optax.warmup_cosine_decay_schedule(0, lr, W, N, lr * r)`` under
   ``scale_by_schedule``, evaluated on the device once per step from the step counter (``csrc/elementwise.hip``), so
   a captured step replays the schedule instead of one frozen rate; :meth:`OptimConfig.lr_at` is its float64 value.
+* ``TrainConfig.eval_every`` (default 0 = off) / ``eval_batches`` (default 8): every ``eval_every`` optimizer updates and
+  after the last one, a forward-only pass over ``eval_batches`` held-out batches of ``batch`` rows (the synthetic
+  stream read from ``data/synthetic.py EVAL_POS_BASE`` on: the same tokens at every evaluation and under every
+  layout) reports mean loss, perplexity and top-1 accuracy: one console line, ``eval.csv`` beside ``log.csv``,
+  ``eval_last`` / ``eval_time_total_s`` in ``metrics.json``.  Its own hipGraph, dropout 0, the training forward's
+  kernels with a lm_head epilogue that stores no logits (``train/engine.py Engine.evaluate``); the training run is bit
+  for bit the one without it, and its clock stops for the duration.  pp = 1; not with ``defer_optimizer`` (parameters
+  are not final between steps) or ``data: fineweb``.
 """
 
 from __future__ import annotations
@@ -261,6 +269,28 @@ class TrainConfig:
     capture_comms: Optional[bool] = None
     device: str = "auto"  # auto | cuda | cpu
     batch_is_global: bool = True  # reference: `batch` is the global batch
+    # held-out evaluation (train/engine.py Engine.evaluate): every eval_every optimizer updates and after the last
+    # one, a forward-only pass over eval_batches held-out batches of `batch` rows -> loss, perplexity, top-1.  0 = off
+    eval_every: int = 0
+    eval_batches: int = 8
+
+    def __post_init__(self):
+        for name in ("eval_every", "eval_batches"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name}={v!r}: expected a non-negative integer")
+        if self.eval_every > 0:
+            if self.eval_batches < 1:
+                raise ValueError(f"eval_every={self.eval_every} needs eval_batches >= 1 (got {self.eval_batches})")
+            if self.defer_optimizer:
+                raise ValueError("eval_every > 0 cannot be combined with defer_optimizer=true (the deferred update "
+                                 "runs under the next step's forward: parameters are not final between steps)")
+            if (self.pp or 1) > 1:  # (parallel: pp resolves to the world size: refused by the engine)
+                raise ValueError("eval_every > 0 needs pp == 1: evaluation under pipeline parallelism is not "
+                                 "implemented (the follow-up: a forward-only pipeline schedule)")
+            if self.data != "synthetic":
+                raise ValueError(f"eval_every > 0 with data={self.data!r}: the held-out set is defined for the "
+                                 "synthetic stream only (data: synthetic)")
 
 
 # Named model presets.  "ref" is the reference's configs/model_config.yaml.

@@ -41,6 +41,7 @@ struct GemmArgs {
                      // batched reducer sums them later) instead of launching splitk_reduce
   float* colsum;     // layout 2 (register-staged kernel): colsum[z*M + m] = sum over split z's k-range
                      // of A(k, m) — the bias gradient of the same dY, fused into its weight gradient
+  int* part_arg;     // EPI_LMHEAD_EVAL: int32 [nparts][M], the shard-local column of each part's row maximum
 };
 
 // Grouped weight gradients (csrc/gemm.hip gemm8p_group_kernel, ops/gemm.py wgrad_group): problem i is
@@ -98,6 +99,8 @@ struct RedBatch {
 enum { EPI_STORE = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_DGELU = 3, EPI_LMHEAD = 4,
        EPI_RESID_LN = 5,  // x = resid + acc + bias (fp32 C) and y = LayerNorm(x) (bf16) + row mean/rstd
        EPI_LN_BWD = 6,    // acc = dy: C = dres + LayerNorm'(dy) (fp32) + bf16 copy + dgamma/dbeta/dbias partials
+       EPI_LMHEAD_EVAL = 7,  // EPI_LMHEAD's row statistics and label logit without the logits store, + the
+                             // per-part row arg-max (GemmArgs.part_arg): the forward-only evaluation head
        EPI_NONE = 99 /* microbench: no store */ };
 
 // Mirror of ops/_native.py LnArgs (keep field order and types identical): a layer GEMM with the

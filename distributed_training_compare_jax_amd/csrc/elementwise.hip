@@ -361,6 +361,107 @@ __global__ void ce_loss_reduce(const float* __restrict__ lse, const float* __res
   }
 }
 
+// ---- evaluation: row arg-max (top-1) from partial arg-maxes
+// (value, column) candidates order by value, ties by the LOWER column; a column < 0 is "no candidate"
+__device__ __forceinline__ void argmax_take(float& bv, int& ba, float v, int a) {
+  if (a >= 0 && (ba < 0 || v > bv || (v == bv && a < ba))) {
+    bv = v;
+    ba = a;
+  }
+}
+
+// Per row: the winner over P candidates (val[row*vrow + p*vpart], arg[row*arow + p*apart]); arg is int32, or
+// fp32 holding an integer (a candidate that travelled with the row statistics through a float gather).
+// Candidates are the lm_head evaluation epilogue's parts (val = the part maximum, arg = its shard-local
+// column) or the winners of R vocab shards (global columns).  Out: argmax[row] = column + col_off (-1: no
+// candidate), optionally its value, and with labels: correct[row] = (argmax == label) and the number of
+// correct rows ADDED to count[0].  Same 16 rows x 16 candidate lanes as ce_combine_rows (row on the fast
+// lane index: the part-major arrays are read in whole lines); lanes and blocks combine with the total
+// order above, and the count is an integer sum (per-block, then one integer atomic per block), so every
+// output is independent of the order the blocks run in.
+__global__ void __launch_bounds__(256) ce_eval_finish_rows(const float* __restrict__ val, long vrow, long vpart,
+                                                           const void* __restrict__ arg, int arg_f32, long arow,
+                                                           long apart, int M, int P, int col_off,
+                                                           const int* __restrict__ labels, int* __restrict__ argmax,
+                                                           float* __restrict__ val_out, int* __restrict__ correct,
+                                                           int* __restrict__ count) {
+  const int r = threadIdx.x % CC_ROWS, pl = threadIdx.x / CC_ROWS;
+  const int row = blockIdx.x * CC_ROWS + r;
+  __shared__ float rv[CC_LANES][CC_ROWS];
+  __shared__ int ra[CC_LANES][CC_ROWS];
+  __shared__ int hit[CC_ROWS];
+  float bv = -INFINITY;
+  int ba = -1;
+  if (row < M) {
+#pragma unroll 4
+    for (int p = pl; p < P; p += CC_LANES) {
+      const long ai = row * arow + p * apart;
+      const int a = arg_f32 ? (int)((const float*)arg)[ai] : ((const int*)arg)[ai];
+      argmax_take(bv, ba, val[row * vrow + p * vpart], a);
+    }
+  }
+  rv[pl][r] = bv;
+  ra[pl][r] = ba;
+  __syncthreads();
+  if (pl == 0) {
+    int ok = 0;
+    if (row < M) {
+#pragma unroll
+      for (int q = 1; q < CC_LANES; ++q) argmax_take(bv, ba, rv[q][r], ra[q][r]);
+      const int col = ba < 0 ? -1 : ba + col_off;
+      argmax[row] = col;
+      if (val_out) val_out[row] = bv;
+      if (labels) {
+        ok = col == labels[row];
+        correct[row] = ok;
+      }
+    }
+    hit[r] = ok;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && labels) {
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < CC_ROWS; ++q) n += hit[q];
+    if (n) atomicAdd(count, n);
+  }
+}
+
+// Streaming row arg-max over stored fp32 logits (the exact-fp32 evaluation head, which keeps its storing
+// lm_head): one block per row, float4 loads, columns >= n_valid never candidates; val[row], arg[row]
+// (row-local column, -1: none).  Same order as above: lowest column among equal maxima.
+__global__ void __launch_bounds__(256) row_argmax_f32_kernel(const float* __restrict__ x, long ld, int M, int n_valid,
+                                                             float* __restrict__ val, int* __restrict__ arg) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* xr = x + (long)row * ld;
+  float bv = -INFINITY;
+  int ba = -1;
+  const int n4 = n_valid & ~3;
+  for (int c = tid * 4; c < n4; c += 256 * 4) {
+    const f32x4 v = *(const f32x4*)(xr + c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) argmax_take(bv, ba, v[k], c + k);
+  }
+  if (tid < n_valid - n4) argmax_take(bv, ba, xr[n4 + tid], n4 + tid);
+  __shared__ float sv[256];
+  __shared__ int sa[256];
+  sv[tid] = bv;
+  sa[tid] = ba;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) {
+      argmax_take(bv, ba, sv[tid + s], sa[tid + s]);
+      sv[tid] = bv;
+      sa[tid] = ba;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    val[row] = bv;
+    arg[row] = ba;
+  }
+}
+
 // dlogits = (exp(l - lse) - onehot) * scale (common.h ce_grad8), in place, 8 bf16 per thread
 __global__ void ce_bwd_kernel(bf16* __restrict__ logits, long ld, const float* __restrict__ lse,
                               const int* __restrict__ labels, int M, int V, int vstart, int n_valid, float scale) {
@@ -881,6 +982,29 @@ int dtc_ce_combine(const float* part, int M, int P, long srow, long spart, const
     hipLaunchKernelGGL(ce_loss_reduce, dim3(1), dim3(1024), 0, st, lse, label_logit, M, loss_scale, loss_out, accumulate);
     DTC_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+// Evaluation top-1 (ce_eval_finish_rows): strides in elements; arg_f32 != 0: the candidates' columns are
+// fp32-held integers.  labels / correct / count all given or all null.
+int dtc_ce_eval_finish(const float* val, long vrow, long vpart, const void* arg, int arg_f32, long arow, long apart,
+                       int M, int P, int col_off, const int* labels, int* argmax, float* val_out, int* correct,
+                       int* count, hipStream_t st) {
+  if (M <= 0) return 0;
+  if (!val || !arg || !argmax || P < 1) return 3005;
+  if ((labels != nullptr) != (correct != nullptr) || (labels != nullptr) != (count != nullptr)) return 3005;
+  hipLaunchKernelGGL(ce_eval_finish_rows, dim3((M + CC_ROWS - 1) / CC_ROWS), dim3(256), 0, st, val, vrow, vpart, arg,
+                     arg_f32, arow, apart, M, P, col_off, labels, argmax, val_out, correct, count);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+// Row arg-max over the first n_valid columns of stored fp32 logits [M][ld] (row_argmax_f32_kernel)
+int dtc_row_argmax_f32(const float* x, long ld, int M, int n_valid, float* val, int* arg, hipStream_t st) {
+  if (M <= 0) return 0;
+  if (!x || !val || !arg || n_valid < 0 || n_valid > ld || ld % 4 || ((unsigned long)x % 16)) return 3006;
+  hipLaunchKernelGGL(row_argmax_f32_kernel, dim3(M), dim3(256), 0, st, x, ld, M, n_valid, val, arg);
+  DTC_CHECK_LAUNCH();
   return 0;
 }
 

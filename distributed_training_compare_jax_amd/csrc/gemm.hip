@@ -157,6 +157,7 @@ struct Epi {
   const int* labels; int vocab_start, n_valid;
   float* part; int nparts;
   float* label_out;
+  int* part_arg;  // EPI_LMHEAD_EVAL: [nparts][M] shard-local column of the part's row maximum (-1: no valid column)
   float* colsum;
   int cs_accum;  // colsum IS the bias gradient: colsum[m] = beta*colsum[m] + sum (split == 1 only)
   float* sq;     // gemm8p_tile, fp32 store: per-wave sums of squares of the stored values (8 slots)
@@ -632,6 +633,14 @@ __device__ __forceinline__ void ln_bwd_epilogue(const f32x4 (&acc)[TN][TM], floa
   }
 }
 
+constexpr bool is_lmhead(int epi) { return epi == EPI_LMHEAD || epi == EPI_LMHEAD_EVAL; }
+
+// DTC_EVAL_ARGMAX=0: the evaluation epilogue without its arg-max (part_arg is left unwritten) -- a
+// measuring probe for the arg-max's share of the launch (profiles/eval.md), never a shipped configuration
+#ifndef DTC_EVAL_ARGMAX
+#define DTC_EVAL_ARGMAX 1
+#endif
+
 // lm_head epilogue: logits (bf16) + per-row partial (max, sum exp) over this wave's TN*16 columns +
 // the label logit.  acc[i][j]: lane holds C[m_base + 16j + (lane&15)][n_base + 16i + 4(lane>>4) + r].
 // Epilogue operands loaded up front (all loads in flight together, ideally before the main loop
@@ -668,10 +677,24 @@ __device__ __forceinline__ void epi_prefetch(const Epi& e, int m_base, int n_bas
 // wave is a real vocab entry (all tiles but the last), so no per-element validity selects.  The
 // staged form reads the label logit back from the LDS stage (one read per row) instead of
 // comparing every element against the label, and folds (v - max)*log2(e) into one fma.
-template <int TN, int TM, bool FULL, bool STAGED, bool ACCB>
+//
+// EVAL (EPI_LMHEAD_EVAL, the forward-only evaluation head): the same (max, sum exp) and label logit, bit
+// for bit (the same bf16-rounded values through the same operations in the same order), NO logits store
+// (e.C may be null), and the part's row arg-max -> e.part_arg[part][m]: the shard-local column of the
+// lowest valid column whose rounded logit equals the part's row maximum, -1 when the wave has no valid
+// column (or every valid logit is NaN).  It is found AFTER the wave-wide maximum is known: each lane
+// takes the lowest of its 16 columns that equals it (a descending scan of compare + select, so the lowest
+// wins), then an integer min over the four lane groups -- the same "lowest index wins" as carrying
+// (value, index) pairs through the two shuffles, with two integer shuffles instead of four and no second
+// value compare.  Both kernels take the label logit by comparing against pre.lab here, the staged 256^2
+// one too: with no logits to store the LDS stage would exist only for that read-back (32 ds_write_b64 +
+// 2 ds_read per lane and an LDS round trip), while the compare is 3 VALU ops per 4-column group whose
+// operands are already in registers; pre.labr is then dead and pre.lab (8 VGPRs) takes its place.
+template <int TN, int TM, bool FULL, bool STAGED, bool ACCB, bool EVAL>
 __device__ __forceinline__ void lmhead_rows(const f32x4 (&acc)[TN][TM], const Epi& e, int m_base, int n_base,
                                             int part_idx, int lane, const EpiPre<TN, TM>& pre, bf16* stage) {
   constexpr float L2E = 1.4426950408889634f;
+  constexpr int NOCOL = 0x7fffffff;
   const int g4 = 4 * (lane >> 4);
   bool okv[TN][4];
 #pragma unroll
@@ -698,20 +721,31 @@ __device__ __forceinline__ void lmhead_rows(const f32x4 (&acc)[TN][TM], const Ep
         v[i][r] = okv[i][r] ? rv[r] : -INFINITY;
         mx = fmaxf(mx, v[i][r]);
       }
-      if (!FULL) {
+      if (!FULL && !EVAL) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) if (!okv[i][r]) ob[r] = f2bf(-INFINITY);
       }
-      if (STAGED) {
+      if (STAGED && !EVAL) {
         stage_put(stage, j * 16 + (lane & 15), i * 4 + (lane >> 4), ob);
       } else {
-        if (mvalid && n + 4 <= e.N) *(bf16x4*)((bf16*)e.C + (long)m * e.ldc + n) = ob;
-        const int lab = pre.lab[j];
+        if (!EVAL && mvalid && n + 4 <= e.N) *(bf16x4*)((bf16*)e.C + (long)m * e.ldc + n) = ob;
+        const int lab = pre.lab[j];  // (-1 for rows past M: never matches)
         if (lab >= n && lab < n + 4 && lab < e.n_valid) e.label_out[m] = v[i][lab - n];
       }
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (EVAL && DTC_EVAL_ARGMAX) {
+      int am = NOCOL;
+#pragma unroll
+      for (int i = TN - 1; i >= 0; --i)
+#pragma unroll
+        for (int r = 3; r >= 0; --r)
+          if (okv[i][r] && v[i][r] == mx) am = n_base + i * 16 + g4 + r;
+      am = min(am, __shfl_xor(am, 16, 64));
+      am = min(am, __shfl_xor(am, 32, 64));
+      if (mvalid && lane < 16) e.part_arg[(long)part_idx * e.M + m] = am == NOCOL ? -1 : am;
+    }
     float sum = 0.f;
     if (FULL || mx != -INFINITY) {
       const float mxl = mx * L2E;
@@ -726,7 +760,7 @@ __device__ __forceinline__ void lmhead_rows(const f32x4 (&acc)[TN][TM], const Ep
     // part-major [nparts][M]: the 16 rows of a fragment write one contiguous 128-B line
     if (mvalid && lane < 16) *(f32x2*)(e.part + ((long)part_idx * e.M + m) * 2) = f32x2{mx, sum};
   }
-  if (STAGED) {
+  if (STAGED && !EVAL) {
     // label logit: row q*64 + lane, if its label falls in this wave's columns (same wave wrote the
     // stage: LDS ops of one wave complete in order)
 #pragma unroll
@@ -744,13 +778,13 @@ __device__ __forceinline__ void lmhead_rows(const f32x4 (&acc)[TN][TM], const Ep
 // Epilogue operands loaded up front (all loads in flight together, ideally before the main loop
 // ends): one bias vector per column group and one label per fragment row.  ACCB: the accumulators
 // started from the bias (the main loop added onto it), so no bias add here.
-template <int TN, int TM, bool STAGED = false, bool ACCB = false>
+template <int TN, int TM, bool STAGED = false, bool ACCB = false, bool EVAL = false>
 __device__ __forceinline__ void lmhead_epilogue(const f32x4 (&acc)[TN][TM], const Epi& e, int m_base, int n_base,
                                                 int part_idx, int lane, const EpiPre<TN, TM>& pre,
                                                 bf16* stage = nullptr) {
   const bool full = n_base + TN * 16 <= min(e.n_valid, e.N);  // wave-uniform
-  if (full) lmhead_rows<TN, TM, true, STAGED, ACCB>(acc, e, m_base, n_base, part_idx, lane, pre, stage);
-  else lmhead_rows<TN, TM, false, STAGED, ACCB>(acc, e, m_base, n_base, part_idx, lane, pre, stage);
+  if (full) lmhead_rows<TN, TM, true, STAGED, ACCB, EVAL>(acc, e, m_base, n_base, part_idx, lane, pre, stage);
+  else lmhead_rows<TN, TM, false, STAGED, ACCB, EVAL>(acc, e, m_base, n_base, part_idx, lane, pre, stage);
 }
 
 // LDS elements of the register-staged kernel (two stages of A and B tiles)
@@ -968,10 +1002,11 @@ __device__ __forceinline__ void gemm_body(bf16* smem, int bid, const bf16* __res
                                         EPI == EPI_STORE ? e.beta : 0.f);
     return;
   }
-  if (EPI == EPI_LMHEAD) {
+  if (is_lmhead(EPI)) {
     EpiPre<TN, TM> pre;
     epi_prefetch<TN, TM>(e, m0 + wm * WM, n0 + wn * WN, lane, true, pre);
-    lmhead_epilogue<TN, TM>(acc, e, m0 + wm * WM, n0 + wn * WN, tn_idx * 2 + wn, lane, pre);
+    lmhead_epilogue<TN, TM, false, false, EPI == EPI_LMHEAD_EVAL>(acc, e, m0 + wm * WM, n0 + wn * WN, tn_idx * 2 + wn,
+                                                                  lane, pre);
     return;
   }
   if constexpr (EPI == EPI_NONE) {  // microbenchmark: main loop only (keep the accumulators live)
@@ -1276,7 +1311,7 @@ __device__ __forceinline__ void gemm8p_tile_s(bf16* smem, const bf16* __restrict
                                               const Epi& e) {
   constexpr int TM = 8, TN = CB;  // 16x16 fragments per wave: 128 (m) x 16*CB (n)
   constexpr int WN = 16 * CB;     // columns per wave
-  static_assert(CB == 4 || (EPI != EPI_LMHEAD), "the CE epilogue assumes 64-column waves");
+  static_assert(CB == 4 || !is_lmhead(EPI), "the CE epilogue assumes 64-column waves");
   static_assert(CB >= 1 && CB <= 4, "1..4 column chunks of 64");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;  // M half (= wave group), 64-column slice
@@ -1301,8 +1336,8 @@ __device__ __forceinline__ void gemm8p_tile_s(bf16* smem, const bf16* __restrict
   // it in the epilogue (16 fewer registers live through the main loop)
   constexpr bool PRE_BIAS = EDGE && CB == 4 && EPI == EPI_STORE && !OUTF32;
   EpiPre<TN, TM> pre;  // epilogue operands: loaded ahead of every DMA, retired by the prologue wait
-  if (split == 1 && (EPI == EPI_LMHEAD || PRE_BIAS))
-    epi_prefetch<TN, TM>(e, m0 + wr * 128, n0 + wc * WN, lane, EPI == EPI_LMHEAD, pre);
+  if (split == 1 && (is_lmhead(EPI) || PRE_BIAS))
+    epi_prefetch<TN, TM>(e, m0 + wr * 128, n0 + wc * WN, lane, is_lmhead(EPI), pre);
   // prologue: B(0), A(0), B(1) in flight; wait for the first two
 #pragma unroll
   for (int q = 0; q < CB; ++q) dmaB(0, q);
@@ -1315,7 +1350,7 @@ __device__ __forceinline__ void gemm8p_tile_s(bf16* smem, const bf16* __restrict
   } else {
     P8_VMCNT(0);
   }
-  if (EPI == EPI_LMHEAD && split == 1) {  // the bias is the accumulators' starting value
+  if (is_lmhead(EPI) && split == 1) {  // the bias is the accumulators' starting value
 #pragma unroll
     for (int i = 0; i < TN; ++i)
 #pragma unroll
@@ -1422,8 +1457,9 @@ __device__ __forceinline__ void gemm8p_tile_s(bf16* smem, const bf16* __restrict
     return;
   }
   bf16* stage = smem + wave * (128 * 64);
-  if constexpr (CB == 4 && EPI == EPI_LMHEAD) {
-    lmhead_epilogue<TN, TM, true, true>(acc, e, m0 + wr * 128, n0 + wc * 64, tn_idx * 4 + wc, lane, pre, stage);
+  if constexpr (CB == 4 && is_lmhead(EPI)) {
+    lmhead_epilogue<TN, TM, true, true, EPI == EPI_LMHEAD_EVAL>(acc, e, m0 + wr * 128, n0 + wc * 64, tn_idx * 4 + wc, lane,
+                                                                 pre, stage);
     return;
   }
   // staged bf16 epilogue: the 256^2 kernels' plain stores, gemm8r's plain, GELU-pair and dGELU stores
@@ -2718,7 +2754,7 @@ GemmLaunch make_launch(const GemmArgs& a, const Plan& p) {
   e = Epi{};
   e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
   e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
-  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out;
+  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg;
   e.colsum = a.colsum;
   g.tiles_m = (a.M + BM - 1) / BM;
   g.tiles_n = (a.N + BN - 1) / BN;
@@ -2742,7 +2778,7 @@ int launch_t(const GemmArgs& a, const Plan& p, hipStream_t st) {
   Epi e{};
   e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
   e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
-  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out;
+  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg;
   e.colsum = a.colsum;
   int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
   e.nparts = tiles_n * 2;
@@ -2862,7 +2898,7 @@ int launch_big(const GemmArgs& a, int split, hipStream_t st) {
   Epi e{};
   e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
   e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
-  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out;
+  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg;
   e.colsum = a.colsum;  // fused bias gradient (gemm8p_kernel, layout TN only)
   const int tiles_m = (a.M + BIG - 1) / BIG, tiles_n = (a.N + BIG - 1) / BIG;
   e.nparts = tiles_n * 4;
@@ -3154,7 +3190,7 @@ int launch_w(const GemmArgs& a, int split, hipStream_t st) {
   Epi e{};
   e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
   e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
-  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.colsum = nullptr;
+  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg; e.colsum = nullptr;
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
   e.nparts = tiles_n * WGN;
   const int ntiles = tiles_m * tiles_n;
@@ -3429,8 +3465,12 @@ int dtc_gemm(const GemmArgs* a, hipStream_t st) {
   if (a->K % 32 != 0) return 1001;               // K must be a multiple of 32 (BK = 64, or 32)
   if (a->lda % 8 || a->ldb % 8 || a->ldc % 4) return 1002;  // 16-B row alignment
   if (a->M <= 0 || a->N <= 0) return 0;
-  const int epi = a->epi;
+  // the evaluation head plans as the training head (same kernel family, tile and part count); only the
+  // two dispatch sites that carry EPI_LMHEAD tell them apart
+  const bool eval = a->epi == EPI_LMHEAD_EVAL;
+  const int epi = eval ? EPI_LMHEAD : a->epi;
   const bool f32 = a->c_f32 != 0;
+  if (eval && (a->layout != 0 || f32 || !a->part_arg || !a->part || !a->label_out || !a->labels)) return 1011;
   if (a->layout <= 1 && !a->colsum && a->alpha == 1.f && a->beta == 0.f &&
       !n8_cb(a->layout, a->M, a->N, a->K, epi)) {
     const R8Plan pl = r8_plan(a->layout, a->M, a->N, a->K, epi, f32);
@@ -3474,7 +3514,9 @@ int dtc_gemm(const GemmArgs* a, hipStream_t st) {
     if (bs0 > 1 && epi == EPI_STORE && f32 && a->bias) return 1010;
     if (bs0 > 1 && epi == EPI_STORE && f32) return launch_big<true, true, EPI_STORE, true>(*a, bs0, st);
     if (bs0 == 1) {
-      if (epi == EPI_LMHEAD) return launch_big<true, true, EPI_LMHEAD, false>(*a, 1, st);
+      if (epi == EPI_LMHEAD)
+        return eval ? launch_big<true, true, EPI_LMHEAD_EVAL, false>(*a, 1, st)
+                    : launch_big<true, true, EPI_LMHEAD, false>(*a, 1, st);
       if (epi == EPI_GELU) return launch_big<true, true, EPI_GELU, false>(*a, 1, st);
       if (epi == EPI_DGELU && !f32) return launch_big<true, true, EPI_DGELU, false>(*a, 1, st);
       if (epi == EPI_RESID) return launch_big<true, true, EPI_RESID, true>(*a, 1, st);
@@ -3485,7 +3527,8 @@ int dtc_gemm(const GemmArgs* a, hipStream_t st) {
     if (epi == EPI_LMHEAD) {
       if (p.bk != 64) return 1008;
       p.bm = p.bn = 128;
-      return launch_t<128, 128, true, true, EPI_LMHEAD, false>(*a, p, st); }
+      return eval ? launch_t<128, 128, true, true, EPI_LMHEAD_EVAL, false>(*a, p, st)
+                  : launch_t<128, 128, true, true, EPI_LMHEAD, false>(*a, p, st); }
     if (epi == EPI_GELU) return launch_sz<true, true, EPI_GELU, false>(*a, p, st);
     if (epi == EPI_DGELU && !f32) return launch_sz<true, true, EPI_DGELU, false>(*a, p, st);  // NT dgrad (W^T)
     if (epi == EPI_RESID) return launch_sz<true, true, EPI_RESID, true>(*a, p, st);

@@ -126,6 +126,33 @@ class SyntheticTokenStream:
         return self.tokens(base, nrows * seq_len).reshape(nrows, seq_len)
 
 
+# ---- held-out evaluation set: the same stream (same seed, so the same rank_to_id / succ structure the model is
+# learning), read from a fixed position base far past anything training reads.  Training batch s, row r reads
+# positions [(s * batch + r) * seq_len - 1, (s * batch + r + 1) * seq_len) (a token looks one position back),
+# so a run of S steps in all (warmup, resumed steps and timed steps) stays below S * batch * seq_len; the
+# evaluation rows start at EVAL_POS_BASE and are disjoint from it while S * batch * seq_len < EVAL_POS_BASE
+# (check_heldout_disjoint).  2^48 positions: 5.6e8 steps of GPT-2 small's 512 x 1025 tokens, and
+# base + any evaluation set stays far inside the sampler's signed 64-bit positions.
+EVAL_POS_BASE = 1 << 48
+
+
+def check_heldout_disjoint(total_steps: int, batch: int, seq_len: int):
+    """Raise if a run of ``total_steps`` training batches of ``batch`` rows of ``seq_len`` tokens would read
+    positions of the held-out evaluation set."""
+    if int(total_steps) * int(batch) * int(seq_len) >= EVAL_POS_BASE:
+        raise ValueError(f"steps x batch x seq_len = {total_steps} x {batch} x {seq_len} reaches the held-out "
+                         f"evaluation set's first position {EVAL_POS_BASE}: the evaluation would not be held out")
+
+
+def heldout_rows(stream: SyntheticTokenStream, index: int, row0: int, nrows: int, batch: int,
+                 seq_len: int) -> np.ndarray:
+    """Rows [row0, row0+nrows) of held-out evaluation batch ``index`` (``batch`` rows of ``seq_len`` tokens):
+    a pure function of (seed, index, row), so the same tokens at every evaluation and under every layout,
+    and a rank generates only its own rows."""
+    base = EVAL_POS_BASE + (int(index) * int(batch) + int(row0)) * int(seq_len)
+    return stream.tokens(base, nrows * seq_len).reshape(nrows, seq_len)
+
+
 def get_tokenizer():
     """Reference ``get_tokenizer`` (GPT-2 + <pad>, len 50258).
 

@@ -20,6 +20,7 @@ on the CPU oracle path); all accumulation fp32; grads fp32.
 
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
@@ -309,18 +310,21 @@ class GPTStage:
 
     # ------------------------------------------------------------------ embed
     def embed_forward(self, ids: torch.Tensor, step: torch.Tensor, row0: int, ctx: Dict,
-                      want_keys: bool = True, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      want_keys: bool = True, keys: Optional[torch.Tensor] = None,
+                      dropout: Optional[float] = None) -> torch.Tensor:
         """ids int32 [b, T] → h fp32 [b*T, D]  (wte gather + wpe + dropout, GPTModel.py:30-38).
 
         ``keys``: the backward's sort keys, already computed on the host (``E.embed_sort_keys_host``);
-        otherwise (``want_keys``) they are sorted on the device."""
+        otherwise (``want_keys``) they are sorted on the device.  ``dropout``: the rate instead of the
+        model's (evaluation: 0; ``step`` is then read by nothing)."""
         f = self.flat
+        p_drop = self.cfg.dropout if dropout is None else float(dropout)
         if self.sp:  # this rank's sequences only (the backward gathers the output grads of all of them)
             bl = ids.shape[0] // self.tp.size
             r0 = self.tp.rank * bl
-            h = E.embed_fwd(ids[r0:r0 + bl], f.p("wte"), f.p("wpe"), self.cfg.dropout, self.seed, step, row0 + r0)
+            h = E.embed_fwd(ids[r0:r0 + bl], f.p("wte"), f.p("wpe"), p_drop, self.seed, step, row0 + r0)
         else:
-            h = E.embed_fwd(ids, f.p("wte"), f.p("wpe"), self.cfg.dropout, self.seed, step, row0)
+            h = E.embed_fwd(ids, f.p("wte"), f.p("wpe"), p_drop, self.seed, step, row0)
         if keys is not None:
             ctx["embed"] = (ids, row0, (keys, None))
         else:
@@ -698,10 +702,26 @@ class GPTStage:
                               out_c=dx_c, dbias=None if bias_grad is None else f.g(bias_grad), red=self.red)
         return dx, (dx if dx_c is None else dx_c)
 
-    def stage_forward(self, x: torch.Tensor, batch: int, ctx: Dict) -> torch.Tensor:
+    def stage_forward(self, x: torch.Tensor, batch: int, ctx: Dict, keep: bool = True) -> torch.Tensor:
+        """``keep=False`` (a forward that no backward follows): each layer's saved activations are dropped as
+        soon as the layer returns, so the peak is one layer's, not the stage's."""
         for l in self.layout.layers:
             x = self.block_forward(l, x, batch, ctx)
+            if not keep:
+                del ctx[l]
         return x
+
+    @contextlib.contextmanager
+    def forward_only(self):
+        """Around an evaluation forward: the GEMM-fused LayerNorm is off.  Its row-statistics exchange is one
+        call per site and step with epoch flags keyed on the step counter, which an evaluation does not
+        advance, so a second forward inside a step's epoch would read the first one's flags as its own; the
+        LayerNorms run as their own kernels instead (as they do under every layout without the fusion)."""
+        fuse, self._fuse_fwd = self._fuse_fwd, False
+        try:
+            yield
+        finally:
+            self._fuse_fwd = fuse
 
     # ------------------------------------------------------------------ head
     def head_forward(self, x: torch.Tensor, labels: torch.Tensor, loss_scale: float, ctx: Dict,
@@ -730,6 +750,44 @@ class GPTStage:
         lse, loss = X.ce_finalize(rowstats, lab_logit, loss_scale, loss_out, accumulate)
         ctx["head"] = (x, yf, muf, rsf, logits, lse, lab)
         return loss
+
+    def head_eval(self, x: torch.Tensor, labels: torch.Tensor, out, loss_scale: float = 1.0,
+                  accumulate: bool = False, ctx: Optional[Dict] = None):
+        """Forward-only head: final LN + the logits-free lm_head + CE + top-1 (``ops/xent.py``
+        ``lmhead_eval_partials`` / ``ce_eval_finish``).  ``out = (loss, count)``: ``loss`` (1-element fp32)
+        gets ``loss_scale · Σ_tokens CE`` exactly as :meth:`head_forward` computes it -- the same row statistics
+        through the same ``ce_finalize`` -- written, or added to with ``accumulate``; ``count`` (1-element int32)
+        has the rows whose arg-max is the label ADDED to it.  Returns ``(argmax [M] int32, correct [M] int32)``.
+
+        Under vocab-parallel TP the shards exchange what the training head exchanges, the row statistics
+        extended by each shard's winning column (global, as fp32: exact below 2^24) in the same gather, and
+        the label logit's all-reduce.  It holds no logits, so DTC_CE_CHUNK and DTC_CE_FUSED do not apply.
+        ``ctx``: an ``lnf_pre`` the last block's LayerNorm pass left there is used, as in training."""
+        self._await_params("head")
+        f = self.flat
+        pre = ctx.pop("lnf_pre", None) if ctx is not None else None
+        if pre is None:
+            pre = LN.layernorm_fwd(x, f.p("lnf.g"), f.p("lnf.b"), self.eps, self.act_dtype)
+        yf = pre[0]
+        if self.sp:
+            yf = self.tp.all_gather_rows(yf)
+        lab = labels.reshape(-1)
+        loss, count = out
+        tp1 = self.tp.size == 1
+        part, lab_logit, cval, ccol = X.lmhead_eval_partials(yf, f.w("lm_head.w"), f.p("lm_head.b"), lab, self.v_start,
+                                                             self.v_valid, single_shard=tp1)
+        if tp1:
+            rowstats = part
+            am, _, correct = X.ce_eval_finish(cval, ccol, self.v_start, lab, count)
+        else:
+            mine, _, _ = X.ce_eval_finish(cval, ccol, self.v_start)  # this shard's winner, as a global column
+            pack = torch.cat([X.combine_partials(part), mine.to(torch.float32)[:, None]], 1)  # [M, 3]
+            g = self.tp.all_gather_stack(pack)  # [tp, M, 3], shards in vocab order
+            self.tp.all_reduce_(lab_logit)
+            rowstats = g[:, :, :2].contiguous()
+            am, _, correct = X.ce_eval_finish(g[:, :, 0], g[:, :, 2], 0, lab, count)
+        X.ce_finalize(rowstats, lab_logit, loss_scale, loss, accumulate)
+        return am, correct
 
     # ------------------------------------------------------------------ head split over two pipeline stages
     def head_split_logits(self, x: torch.Tensor, labels: torch.Tensor, ctx: Dict) -> torch.Tensor:

@@ -55,7 +55,17 @@ class _FakeQuantLinear(torch.autograd.Function):
 def oracle_loss(cfg: ModelConfig, params: dict, ids: torch.Tensor, labels: torch.Tensor, seed: int, step: int,
                 row0: int = 0, fake_quant: bool = False, quant_bf16_inputs: bool = False,
                 quant_inputs: list = None) -> torch.Tensor:
-    """params: name → fp32 tensor (full shapes, [out,in] Dense layout), requires_grad allowed.
+    """Mean cross-entropy of :func:`oracle_logits` (same arguments) against ``labels``."""
+    logits = oracle_logits(cfg, params, ids, seed, step, row0, fake_quant, quant_bf16_inputs, quant_inputs)
+    V = cfg.vocab_size
+    return F.cross_entropy(logits.reshape(-1, V), labels.reshape(-1).long())
+
+
+def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, step: int,
+                  row0: int = 0, fake_quant: bool = False, quant_bf16_inputs: bool = False,
+                  quant_inputs: list = None) -> torch.Tensor:
+    """Logits ``[B, T, vocab_size]``.  params: name → fp32 tensor (full shapes, [out,in] Dense layout),
+    requires_grad allowed.
 
     ``fake_quant`` (default off): the four layer GEMMs of every block (qkv, out_proj, fc1, fc2) run as
     :class:`_FakeQuantLinear`, the statement of ``TrainConfig.fwd_gemm_dtype: fp8``; the lm_head stays as it is.
@@ -96,5 +106,4 @@ def oracle_loss(cfg: ModelConfig, params: dict, ids: torch.Tensor, labels: torch
         h = mm(x, p("fc2.w")) + p("fc2.b") + r
     x = F.layer_norm(h, (D,), params["lnf.g"], params["lnf.b"], eps)
     V = cfg.vocab_size
-    logits = x @ params["lm_head.w"][:V].t() + params["lm_head.b"][:V]
-    return F.cross_entropy(logits.reshape(-1, V), labels.reshape(-1).long())
+    return x @ params["lm_head.w"][:V].t() + params["lm_head.b"][:V]

@@ -55,6 +55,7 @@ class GemmArgs(ctypes.Structure):
         ("split_k", c_int),      # 0 = auto
         ("defer_reduce", c_int),  # wgrad split-K: leave the slabs in `workspace` (ops/reduce.py)
         ("colsum", c_vp),        # wgrad: fp32 [split][M] bias-gradient partials (fused colsum)
+        ("part_arg", c_vp),      # EPI_LMHEAD_EVAL: int32 [nparts][M] per-part row arg-max (shard-local column)
     ]
 
 
@@ -98,6 +99,7 @@ EPI_RESID = 1       # C(f32) = aux(f32) + acc + bias
 EPI_GELU = 2        # u = acc+bias: C(bf16) = gelu_tanh'(u) ; aux_out(bf16) = gelu_tanh(u)
 EPI_DGELU = 3       # C(bf16) = acc * aux   (aux = gelu_tanh'(u) from EPI_GELU)
 EPI_LMHEAD = 4      # C(bf16) = acc+bias, pad cols -inf; per-row partial (max,sumexp); label logit
+EPI_LMHEAD_EVAL = 7  # EPI_LMHEAD's partials and label logit, no logits store (C null), + per-part row arg-max
 
 
 def _declare(lib):
@@ -167,6 +169,8 @@ def _declare(lib):
         "dtc_attn_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, l, vp], i),
         "dtc_attn_bwd_workspace_bytes": ([i, i, i, i], l),
         "dtc_ce_combine": ([vp, i, i, l, l, vp, vp, vp, f, vp, i, vp], i),
+        "dtc_ce_eval_finish": ([vp, l, l, vp, i, l, l, i, i, i, vp, vp, vp, vp, vp, vp], i),
+        "dtc_row_argmax_f32": ([vp, l, i, i, vp, vp, vp], i),
         "dtc_ce_bwd": ([vp, l, vp, vp, i, i, i, i, f, vp, vp], i),
         "dtc_ce_colsum_rows": ([], i),
         "dtc_sumsq_segments": ([vp, vp, i, vp, vp, vp, l, vp], i),

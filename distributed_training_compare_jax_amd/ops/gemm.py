@@ -91,16 +91,16 @@ def reserve_workspace(device, nbytes: int, role: str = "main"):
 def _gemm_native(layout: int, M: int, N_: int, K: int, a, lda: int, b, ldb: int, c, ldc: int, **kw):
     args = _gemm_args(layout, M, N_, K, a, lda, b, ldb, c, ldc, **kw)
     if a.dtype == torch.float32:
-        N.check(N.lib().dtc_gemm_f32(args, N.stream_ptr(c.device)), "dtc_gemm_f32")
+        N.check(N.lib().dtc_gemm_f32(args, N.stream_ptr(a.device)), "dtc_gemm_f32")
     else:
-        N.check(N.lib().dtc_gemm(args, N.stream_ptr(c.device)), "dtc_gemm")
+        N.check(N.lib().dtc_gemm(args, N.stream_ptr(a.device)), "dtc_gemm")
 
 
 def _gemm_args(layout: int, M: int, N_: int, K: int, a, lda: int, b, ldb: int, c, ldc: int, *,
                epi: int = N.EPI_STORE, bias=None, aux=None, ldaux: int = 0, aux_out=None,
                alpha: float = 1.0, beta: float = 0.0, labels=None, vocab_start: int = 0,
                n_valid: int = 0, part=None, label_out=None, workspace=None, defer_reduce: int = 0,
-               colsum=None) -> "N.GemmArgs":
+               colsum=None, part_arg=None) -> "N.GemmArgs":
     L = N.lib()
     if workspace is not None:
         ws = workspace.view(torch.uint8) if workspace.dtype != torch.uint8 else workspace
@@ -109,16 +109,16 @@ def _gemm_args(layout: int, M: int, N_: int, K: int, a, lda: int, b, ldb: int, c
             ws_need = int(L.dtc_gemm_f32_workspace_bytes(layout, M, N_, K))
         else:
             ws_need = int(L.dtc_gemm_workspace_bytes(layout, M, N_, K))
-        ws = _workspace(c.device, ws_need) if ws_need > 0 else None
+        ws = _workspace(a.device, ws_need) if ws_need > 0 else None
     args = N.GemmArgs(
         layout=layout, M=M, N=N_, K=K,
-        A=a.data_ptr(), lda=lda, B=b.data_ptr(), ldb=ldb, C=c.data_ptr(), ldc=ldc,
-        c_f32=1 if c.dtype == torch.float32 else 0, epi=epi,
+        A=a.data_ptr(), lda=lda, B=b.data_ptr(), ldb=ldb, C=N.ptr(c), ldc=ldc,
+        c_f32=1 if c is not None and c.dtype == torch.float32 else 0, epi=epi,
         bias=N.ptr(bias), aux=N.ptr(aux), ldaux=ldaux, aux_out=N.ptr(aux_out),
         alpha=alpha, beta=beta, labels=N.ptr(labels), vocab_start=vocab_start, n_valid=n_valid,
         part=N.ptr(part), label_out=N.ptr(label_out),
         workspace=N.ptr(ws), ws_bytes=0 if ws is None else ws.numel(), split_k=0, defer_reduce=defer_reduce,
-        colsum=N.ptr(colsum))
+        colsum=N.ptr(colsum), part_arg=N.ptr(part_arg))
     return args
 
 

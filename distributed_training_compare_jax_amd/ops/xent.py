@@ -55,10 +55,106 @@ def lmhead_logits_partials(h: torch.Tensor, w: torch.Tensor, b: torch.Tensor, la
                  labels=labels, vocab_start=vocab_start, n_valid=n_valid, part=part, label_out=lab)
     if not combine:
         return logits, part, lab
-    rowstat = torch.empty(M, 2, dtype=torch.float32, device=h.device)
-    N.check(L.dtc_ce_combine(part.data_ptr(), M, P, 1, M, None, None, rowstat.data_ptr(), 0.0, None, 0,
-                             N.stream_ptr(h.device)), "dtc_ce_combine")
-    return logits, rowstat, lab
+    return logits, combine_partials(part), lab
+
+
+def lmhead_eval_partials(h: torch.Tensor, w: torch.Tensor, b: torch.Tensor, labels: torch.Tensor,
+                         vocab_start: int, n_valid: int, single_shard: bool = True):
+    """The forward-only (evaluation) lm_head: the row statistics of :func:`lmhead_logits_partials` and the
+    arg-max candidates of the local vocab shard, with no logits kept.
+
+    Returns ``(part [P, M, 2], label_logit [M], cand_val [Pa, M], cand_col [Pa, M] int32)``: ``part`` and
+    ``label_logit`` are what ``lmhead_logits_partials(..., combine=False)`` returns, bit for bit; candidate
+    ``p`` of row ``m`` is the shard-local column ``cand_col[p, m]`` (-1: none) holding the value
+    ``cand_val[p, m]``, the lowest valid column among equal maxima.  :func:`ce_eval_finish` picks the row's
+    winner.  Values are the logits rounded to the activation dtype, pad columns never candidates.
+
+    bf16 on the GPU: one GEMM launch with the ``EPI_LMHEAD_EVAL`` epilogue -- no logits are stored and
+    ``cand_val`` is a view of ``part`` (a part's maximum IS the value at its arg-max).  fp32 on the GPU (the
+    exact-fp32 parity mode): the storing head, then a streaming row arg-max over its fp32 logits
+    (``Pa = 1``).  CPU: pure torch, ``P = Pa = 1``.  ``single_shard=False`` (one of several vocab shards:
+    some labels lie outside it): the fp32 head combines its parts as the training head does there
+    (``P = 1``); the bf16 epilogue zeroes ``label_logit`` first either way."""
+    M, D = h.shape
+    Vl = w.shape[0]
+    if N.library_path(h) or h.dtype == torch.float32:
+        logits, part, lab = lmhead_logits_partials(h, w, b, labels, vocab_start, n_valid, combine=not single_shard)
+        if not single_shard:
+            part = part.unsqueeze(0)  # the combined (max, sum exp) as the shard's one part
+        if N.library_path(h):
+            lg = logits.float()  # (rounded to the activation dtype, pads -inf)
+            if n_valid > 0:
+                val, col = lg[:, :n_valid].max(-1)  # torch.max: the first index among equal maxima
+                col = col.to(torch.int32)
+            else:
+                val = torch.full((M,), float("-inf"))
+                col = torch.full((M,), -1, dtype=torch.int32)
+            return part, lab, val[None], col[None]
+        val = torch.empty(1, M, dtype=torch.float32, device=h.device)
+        col = torch.empty(1, M, dtype=torch.int32, device=h.device)
+        N.check(N.lib().dtc_row_argmax_f32(logits.data_ptr(), logits.stride(0), M, n_valid, val.data_ptr(),
+                                           col.data_ptr(), N.stream_ptr(h.device)), "dtc_row_argmax_f32")
+        return part, lab, val, col
+    L = N.lib()
+    P = int(L.dtc_lmhead_nparts(M, Vl, D))
+    part = torch.empty(P, M, 2, dtype=torch.float32, device=h.device)
+    col = torch.empty(P, M, dtype=torch.int32, device=h.device)
+    lab = torch.zeros(M, dtype=torch.float32, device=h.device)  # rows whose label is outside the shard stay 0
+    from .gemm import _gemm_native
+
+    _gemm_native(0, M, Vl, D, h, h.stride(0), w, w.stride(0), None, Vl, epi=N.EPI_LMHEAD_EVAL, bias=b,
+                 labels=labels, vocab_start=vocab_start, n_valid=n_valid, part=part, label_out=lab, part_arg=col)
+    return part, lab, part[:, :, 0], col
+
+
+def combine_partials(part: torch.Tensor) -> torch.Tensor:
+    """``part [P, M, 2]`` → ``rowstat [M, 2]`` (max, Σexp) of the shard: what
+    ``lmhead_logits_partials(combine=True)`` returns for the same partials."""
+    P, M, _ = part.shape
+    if not part.is_cuda:  # (the CPU paths produce one part)
+        assert P == 1
+        return part[0]
+    rowstat = torch.empty(M, 2, dtype=torch.float32, device=part.device)
+    N.check(N.lib().dtc_ce_combine(part.data_ptr(), M, P, 1, M, None, None, rowstat.data_ptr(), 0.0, None, 0,
+                                   N.stream_ptr(part.device)), "dtc_ce_combine")
+    return rowstat
+
+
+def ce_eval_finish(cand_val: torch.Tensor, cand_col: torch.Tensor, col_off: int = 0,
+                   labels: torch.Tensor | None = None, count: torch.Tensor | None = None):
+    """Per row, the winner of ``P`` arg-max candidates ``(cand_val[p, m], cand_col[p, m])``: the largest value,
+    the lowest column among equal values; a negative column is no candidate.  ``cand_col`` is int32, or fp32
+    holding integers (candidates gathered with the row statistics of R vocab shards).
+
+    Returns ``(argmax [M] int32 = column + col_off, or -1; value [M]; correct [M] int32 or None)``.  With
+    ``labels`` (global ids), ``correct = argmax == label`` and the number of correct rows is ADDED to the
+    int32 device counter ``count`` (an integer sum: the same in any order)."""
+    P, M = cand_val.shape
+    assert cand_col.shape == (P, M) and (labels is None) == (count is None)
+    dev = cand_val.device
+    if not cand_val.is_cuda:
+        cols = cand_col.to(torch.int64)
+        v = torch.where(cols >= 0, cand_val.float(), torch.full_like(cand_val, float("-inf"), dtype=torch.float32))
+        best = v.max(0).values
+        win = (v == best[None]) & (cols >= 0)
+        big = torch.iinfo(torch.int64).max
+        col = torch.where(win, cols, torch.full_like(cols, big)).min(0).values
+        am = torch.where(col == big, torch.full_like(col, -1), col + col_off).to(torch.int32)
+        correct = None
+        if labels is not None:
+            correct = (am == labels.reshape(-1).to(torch.int32)).to(torch.int32)
+            count.add_(correct.sum().to(count.dtype))
+        return am, best, correct
+    am = torch.empty(M, dtype=torch.int32, device=dev)
+    val = torch.empty(M, dtype=torch.float32, device=dev)
+    correct = torch.empty(M, dtype=torch.int32, device=dev) if labels is not None else None
+    assert cand_val.dtype == torch.float32 and cand_col.dtype in (torch.int32, torch.float32)
+    assert count is None or (count.dtype == torch.int32 and labels.dtype == torch.int32 and labels.is_contiguous())
+    N.check(N.lib().dtc_ce_eval_finish(cand_val.data_ptr(), cand_val.stride(1), cand_val.stride(0), cand_col.data_ptr(),
+                                       int(cand_col.dtype == torch.float32), cand_col.stride(1), cand_col.stride(0),
+                                       M, P, int(col_off), N.ptr(labels), am.data_ptr(), val.data_ptr(),
+                                       N.ptr(correct), N.ptr(count), N.stream_ptr(dev)), "dtc_ce_eval_finish")
+    return am, val, correct
 
 
 def ce_finalize(rowstats: torch.Tensor, label_logit: torch.Tensor, loss_scale: float,

@@ -248,7 +248,8 @@ class P2PAllReduce(PeerBuffer):
         host does not count (``dtc_p2p_barrier_round``), on every rank, does.  NOT caught: an eager call
         outside the step (eval, a debug all-reduce) without its own :meth:`end_step` advances host and
         device alike, so this check passes, yet the pointers a captured step got from :meth:`staged_out`
-        are then one half off on replay.  Always pad out-of-step use with :meth:`end_step`."""
+        are then one half off on replay.  Always pad out-of-step use with :meth:`end_step`
+        (``Engine.evaluate`` does: its own program ends with one, eager and captured)."""
         e = int(self.err.item())
         if e:
             raise RuntimeError(barrier_timeout_message("P2P all-reduce", "rank", self.rank, e))

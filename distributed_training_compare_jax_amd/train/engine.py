@@ -127,6 +127,15 @@ class Engine:
             if why:
                 raise ValueError(f"grad_accum={k_acc} cannot be combined with {why}")
         self.grad_accum = int(k_acc)
+        # eval_every: the held-out evaluation (evaluate) -- what it does not cover is refused here, by name
+        if train_cfg.eval_every > 0:
+            if pp > 1:
+                raise ValueError(f"eval_every > 0 cannot be combined with pp={pp}: evaluation under pipeline parallelism "
+                                 "is not implemented (the follow-up: a forward-only pipeline schedule)")
+            from ..data.synthetic import check_heldout_disjoint
+
+            # (a resumed run adds its earlier steps: train/loop.py checks again with the checkpoint's step)
+            check_heldout_disjoint(train_cfg.warmup_steps + train_cfg.steps, train_cfg.batch, model_cfg.max_seq_len + 1)
         # lm_head + CE split by vocab over the last two pipeline stages (models/gpt.py head_split_*): auto when
         # the head alone outweighs an even share of the model (GPT-2 small at pp >= 5: 2.9 blocks vs 14.9 / pp)
         hsplit = train_cfg.pp_head_split
@@ -423,6 +432,10 @@ class Engine:
             if train_cfg.pp_comm == "p2p":
                 self._init_pp_p2p(pp)
         self.steps_done = 0
+        # the evaluation program and its static buffers (evaluate): created by the first evaluation, so a run
+        # without one allocates and launches nothing for it
+        self.eval_program: Optional[StepProgram] = None
+        self.evals_done = 0
         # Deferred optimizer (pp == 1, GPU): the step ends with the global norm and the AdamW of
         # the embedding tables only; the rest of the update runs at the START of the next step
         # on a second stream, in forward order and in a few layer groups, each group signalling
@@ -1020,6 +1033,137 @@ class Engine:
             if emb:
                 st.emb_sq = part[nwg:]
         return self.loss
+
+    # ------------------------------------------------------------------ evaluation
+    def _eval_fn(self):
+        """One evaluation batch on the static evaluation inputs: the training forward with dropout 0 and without
+        the GEMM-fused LayerNorm, each layer's saved activations dropped as it returns, the logits-free head.
+        ``eval_loss`` = the batch's mean loss over this rank's rows exactly as the training forward computes it
+        (the local batch as ``grad_accum`` microbatches with the full-batch scale, accumulated in microbatch
+        order), ``eval_count`` = its rows whose arg-max is the label.  Reads the parameters and nothing else of
+        the training state: not the step counter's value (dropout 0), not ``emb_prev`` / ``emb_sq`` / the weight-
+        gradient records (backward-side), and it ends with its own ``end_step`` so the P2P calls of every program
+        stay even (``P2PAllReduce.check``)."""
+        st, T, b, k, mb = self.stage, self.T, self.b_local, self.n_micro, self.mb_rows
+        self.eval_count.zero_()
+        with st.forward_only():
+            for j in range(k):
+                r = slice(j * mb, (j + 1) * mb)
+                ctx: Dict = {}
+                h = st.embed_forward(self.eval_ids[r], self.opt.step_t, self.row0 + j * mb, ctx, want_keys=False,
+                                     dropout=0.0)
+                h = st.stage_forward(h, mb, ctx, keep=False)
+                st.head_eval(h, self.eval_labels[r], (self.eval_loss, self.eval_count), 1.0 / (b * T),
+                             accumulate=j > 0, ctx=ctx)
+                del h, ctx
+        if self.p2p is not None:
+            self.p2p.end_step()
+        return self.eval_loss
+
+    def _eval_setup(self, n_batches: int):
+        """The evaluation program, its static device inputs / outputs and the held-out batches of this rank's
+        rows in pinned host memory (``data/synthetic.py heldout_rows``; built once, re-read by every evaluation)."""
+        from ..data import synthetic
+
+        on_gpu = self.device.type == "cuda"
+        if self.eval_program is None:
+            p = self.program
+            self.eval_program = StepProgram(self.device, use_graph=p.use_graph, capture_comms=p.capture_comms)
+            self.eval_program.sync_comms = p.sync_comms
+            self.eval_program.before_comm = p.before_comm
+            self.eval_ids = torch.zeros(self.b_local, self.T, dtype=torch.int32, device=self.device)
+            self.eval_labels = torch.zeros(self.b_local, self.T, dtype=torch.int32, device=self.device)
+            self.eval_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self.eval_count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._eval_host = torch.zeros(0, 2, self.b_local, self.T, dtype=torch.int32)
+            self._eval_stream = synthetic.SyntheticTokenStream(
+                vocab=min(synthetic.BPE_VOCAB, self.mcfg.vocab_size - 1), seed=self.tcfg.seed)
+        have = self._eval_host.shape[0]
+        if have < n_batches:
+            host = torch.zeros(n_batches, 2, self.b_local, self.T, dtype=torch.int32, pin_memory=on_gpu)
+            host[:have].copy_(self._eval_host)
+            for i in range(have, n_batches):
+                rows = synthetic.heldout_rows(self._eval_stream, i, self.row0, self.b_local, self.global_batch,
+                                              self.T + 1)
+                host[i, 0].copy_(torch.from_numpy(rows[:, :-1]))
+                host[i, 1].copy_(torch.from_numpy(rows[:, 1:]))
+            self._eval_host = host
+        if len(getattr(self, "_eval_out", ())) < n_batches:
+            self._eval_out = [(torch.zeros(1, dtype=torch.float32, pin_memory=on_gpu),
+                               torch.zeros(1, dtype=torch.int32, pin_memory=on_gpu)) for _ in range(n_batches)]
+
+    def evaluate(self, n_batches: Optional[int] = None) -> Dict:
+        """Forward-only pass over the first ``n_batches`` (default ``eval_batches``) held-out batches of ``batch``
+        rows: ``dict(loss, ppl, top1, tokens)`` -- mean loss per token, ``exp(loss)``, the share of tokens whose
+        arg-max logit is the label, and the tokens evaluated -- the same on every rank.
+
+        The device accumulates per batch (fp32 loss in a fixed order, integer count), the host across batches
+        in float64, the DP group with ONE eager all-reduce of a 3-element float64 vector (loss sum, correct,
+        tokens) per evaluation; the TP ranks of a replica hold the same numbers already.  The batches replay the
+        evaluation's own captured program (:meth:`_eval_fn`; the first evaluation runs its first batch eagerly
+        and records on the second, as :meth:`run_step` does), with its own static inputs: the training loop
+        stages the next training batch before it reads the previous loss, so the training buffers are never
+        free.  Blocking.  Refused before the first training step (the eager step that sizes workspaces and
+        initialises the process groups), under pipeline parallelism and with ``defer_optimizer``."""
+        if self.mesh.pp > 1:
+            raise ValueError("evaluate(): evaluation under pipeline parallelism is not implemented (pp == 1 only; "
+                             "the follow-up: a forward-only pipeline schedule)")
+        if self.tcfg.defer_optimizer:
+            raise ValueError("evaluate(): not with defer_optimizer=true (the deferred update runs under the next "
+                             "step's forward: parameters are not final between steps)")
+        if self.tcfg.data != "synthetic":
+            raise ValueError(f"evaluate(): the held-out set is defined for data: synthetic, not {self.tcfg.data!r}")
+        if self.steps_done == 0:
+            raise RuntimeError("evaluate() before the first training step: run one step first (it sizes the "
+                               "workspaces and initialises the process groups the evaluation forward reuses)")
+        n = int(self.tcfg.eval_batches if n_batches is None else n_batches)
+        if n < 1:
+            raise ValueError(f"evaluate(): n_batches={n}: expected >= 1")
+        self._eval_setup(n)
+        p, train_p = self.eval_program, self.tp_comm.program
+        self.tp_comm.program = p  # the evaluation's TP collectives cut (or join) ITS graph, not the training step's
+        try:
+            for i in range(n):
+                self.eval_ids.copy_(self._eval_host[i, 0], non_blocking=True)
+                self.eval_labels.copy_(self._eval_host[i, 1], non_blocking=True)
+                p.begin_step()
+                check = self.evals_done == 0 or (p.use_graph and not p.recorded)
+                if check:
+                    p.collect()
+                if not p.use_graph or (not p.recorded and self.evals_done == 0):
+                    self._eval_fn()
+                elif not p.recorded:
+                    p.record(self._eval_fn)
+                    p.verify("recorded evaluation batch")
+                    p.replay()
+                else:
+                    p.replay()
+                if check and p.sigs is not None:
+                    p.verify("first evaluation batch")
+                self.evals_done += 1
+                lo, co = self._eval_out[i]
+                lo.copy_(self.eval_loss, non_blocking=True)
+                co.copy_(self.eval_count, non_blocking=True)
+        finally:
+            self.tp_comm.program = train_p
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
+        self.check_health()
+        rows_tokens = self.b_local * self.T
+        # per batch: eval_loss = this rank's mean over its b_local * T tokens -> its loss SUM in float64
+        loss_sum = sum(float(lo.item()) for lo, _ in self._eval_out[:n]) * rows_tokens
+        correct = sum(int(co.item()) for _, co in self._eval_out[:n])
+        vec = torch.tensor([loss_sum, float(correct), float(n * rows_tokens)], dtype=torch.float64)
+        if self.dp_comm:
+            g = self.mesh.dp_group
+            if self.dinfo.backend == "nccl":
+                vec = vec.to(self.device)
+            dist.all_reduce(vec, group=g)
+            vec = vec.cpu()
+        tokens = int(vec[2].item())
+        loss = float(vec[0].item()) / tokens
+        return dict(loss=loss, ppl=math.exp(loss) if loss < 700.0 else float("inf"),
+                    top1=float(vec[1].item()) / tokens, tokens=tokens)
 
     def _emb_fused_norm(self) -> bool:
         """The embedding backward alone writes the wte / wpe grads, once per step, and they are final there: dp 1

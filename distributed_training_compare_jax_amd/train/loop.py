@@ -7,6 +7,11 @@ Mirrors ``train/train.py:22-233`` (``train_dp_tp`` / ``train_pp``):
   ``train.py:75-85``), elapsed time cumulative since "Start measuring";
 * every ``log_every`` steps: ``Step: {s} | Avg loss: {mean:.4f} | Average step time: {t:.4f}``;
 * ``Total time: ...`` then ``End``; CSV columns ``step,elapsed_time,loss`` (0-based step).
+* ``eval_every`` > 0 (not in the reference): every that many optimizer updates and after the last one, the held-out
+  evaluation (``Engine.evaluate``) with the training clock stopped -- ``elapsed_time``, the ``Average step time``
+  prints and ``tokens_per_s`` keep measuring training only --, one line
+  ``Eval: {step} | loss: {:.4f} | ppl: {:.2f} | top-1: {:.4f} | time: {:.3f}`` and ``eval.csv``
+  (``step,elapsed_time,eval_loss,eval_ppl,eval_top1,eval_time``) beside ``log.csv``.
 
 Extra (not in the reference): the next batch is generated while the GPU runs the current
 step (same work, overlapped), and a ``metrics.json`` sidecar records tokens/s, the mesh
@@ -52,6 +57,9 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
     start = maybe_resume(eng, train_config)
     if start:
         data = make_data_iter(eng, train_config, model_config, start_step=start)
+    if train_config.eval_every > 0:  # with the steps a resumed run has already read
+        synthetic.check_heldout_disjoint(start + train_config.warmup_steps + train_config.steps, eng.global_batch,
+                                         model_config.max_seq_len + 1)
 
     from ..utils.trace import Tracer
     from ..utils.watchdog import Watchdog
@@ -81,6 +89,19 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
     # blocking float(loss), train/train.py:82-85).  A step that ends on a checkpoint is drained
     # before the next one is enqueued, so the checkpoint holds exactly that step's state.
     pending = None
+    evals, eval_s = [], 0.0  # (step, elapsed_time, result, seconds); eval_s = the time the training clock was stopped
+
+    def evaluate(s):
+        # the pending loss is drained (its elapsed time stamped) before the clock stops, as for a checkpoint
+        nonlocal eval_s
+        te = time.perf_counter()
+        dog.beat(s)
+        with tr.span("eval"):
+            r = eng.evaluate(train_config.eval_batches)
+        dt = time.perf_counter() - te
+        evals.append((s, te - t0 - eval_s, r, dt))
+        eval_s += dt
+        say(f"Eval: {s} | loss: {r['loss']:.4f} | ppl: {r['ppl']:.2f} | top-1: {r['top1']:.4f} | time: {dt:.3f}")
 
     def finish(s, handle):
         nonlocal running
@@ -91,7 +112,7 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
         tr.collect()
         running.append(loss)
         history.append(loss)
-        now = time.perf_counter()
+        now = time.perf_counter() - eval_s  # (the training clock: stopped while an evaluation runs)
         elapsed.append(now - t0)
         if s % train_config.log_every == 0:
             say(f"Step: {s} | Avg loss: {np.mean(running):.4f} | Average step time: {(now - t0) / s:.4f}")
@@ -115,10 +136,15 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
             pending = None
             with tr.span("checkpoint"):
                 maybe_save(eng, train_config, gstep)
+        if train_config.eval_every and (gstep % train_config.eval_every == 0 or step == train_config.steps):
+            if pending is not None:
+                finish(*pending)
+                pending = None
+            evaluate(step)
     if pending is not None:
         finish(*pending)
     eng.flush_optimizer()  # complete the last step's deferred update (timed)
-    t1 = time.perf_counter()
+    t1 = time.perf_counter() - eval_s
     dog.stop()
     say(f"Total time: {t1 - t0}")
     say("End")
@@ -141,6 +167,9 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
                   grad_accum=eng.grad_accum, microbatch_rows=eng.mb_rows,
                   lr_schedule=opt_config.lr_schedule)
     result["tflops_per_gpu"] = result["tflops"] / max(1, dinfo.world)
+    if train_config.eval_every:
+        last = evals[-1][2] if evals else None
+        result.update(eval_last=None if last is None else dict(step=evals[-1][0], **last), eval_time_total_s=eval_s)
     if tr.enabled:
         path = tr.write()
         n_warm = train_config.warmup_steps
@@ -149,9 +178,15 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
     if is_main and write_csv:
         os.makedirs(train_config.output_dir, exist_ok=True)
         _write_csv(os.path.join(train_config.output_dir, "log.csv"), elapsed, history)
+        if train_config.eval_every:
+            with open(os.path.join(train_config.output_dir, "eval.csv"), "w") as f:
+                f.write("step,elapsed_time,eval_loss,eval_ppl,eval_top1,eval_time\n")
+                for s_, e, r, dt in evals:
+                    f.write(f"{s_ - 1},{e},{r['loss']},{r['ppl']},{r['top1']},{dt}\n")
         with open(os.path.join(train_config.output_dir, "metrics.json"), "w") as f:
             json.dump(result, f, indent=2)
     result["history"] = history
+    result["evals"] = [(s_, r) for s_, _, r, _ in evals]
     result["engine"] = eng
     return result
 

@@ -86,11 +86,18 @@ def _spawn_target(args):
               help="roctx ranges + device step times + Chrome trace in <output_dir>/trace/")
 @click.option("--dtype", type=click.Choice(["bf16", "fp32"]), default=None,
               help="compute precision (default bf16; fp32 = the reference's precision on the exact-fp32 kernels)")
+@click.option("--eval_every", type=int, default=None,
+              help="held-out evaluation every N optimizer updates and after the last one (0 = off)")
+@click.option("--eval_batches", type=int, default=None, help="held-out batches per evaluation (default 8)")
 @click.option("--set", "sets", multiple=True, metavar="KEY=VALUE",
               help="any other TrainConfig field, e.g. --set tp_comm=p2p --set pp_schedule=1f1b")
 def main(train_config_path: str, model_config_path: str, optim_config_path: str, nproc, steps, device, log_every,
-         warmup_steps, output_dir, profile, dtype, sets):
+         warmup_steps, output_dir, profile, dtype, eval_every, eval_batches, sets):
     overrides = _parse_sets(sets)
+    if eval_every is not None:
+        overrides["eval_every"] = eval_every
+    if eval_batches is not None:
+        overrides["eval_batches"] = eval_batches
     if dtype is not None:
         overrides["dtype"] = dtype
     if output_dir is not None:

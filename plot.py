@@ -6,6 +6,9 @@
   ≈ steps²/2 × step time, not an average).
 * ``outputs/step_time.png`` (new): the true average step time in ms.
 * ``outputs/scaling.png`` (new, if ``outputs/scaling.json`` exists): tokens/s vs GPUs.
+* With an ``outputs/<strategy>/eval.csv`` (``eval_every`` > 0): that strategy's held-out loss as markers on
+  ``loss.png``, and ``outputs/eval_loss.png`` with every strategy's evaluation-loss series side by side.
+  Without one, the figures are the ones above.
 """
 
 from __future__ import annotations
@@ -33,14 +36,31 @@ def main():
             dfs[n] = pd.read_csv(p)
     if not dfs:
         raise SystemExit("no outputs/{dp,tp,pp}/log.csv found")
+    evs = {}
+    for n in dfs:
+        p = os.path.join(ROOT, n, "eval.csv")
+        if os.path.exists(p):
+            evs[n] = pd.read_csv(p)
     for n, c in zip(NAMES, COLORS):
         if n in dfs:
             plt.plot(dfs[n]["step"], dfs[n]["loss"], label=n, alpha=0.5, color=c)
+        if n in evs:
+            plt.plot(evs[n]["step"], evs[n]["eval_loss"], "o", label=f"{n} held-out", color=c, markersize=4)
     plt.xlabel("step")
     plt.ylabel("loss")
     plt.legend()
     plt.savefig(os.path.join(ROOT, "loss.png"))
     plt.cla()
+
+    if evs:
+        for n, c in zip(NAMES, COLORS):
+            if n in evs:
+                plt.plot(evs[n]["step"], evs[n]["eval_loss"], "o-", label=n, alpha=0.7, color=c)
+        plt.xlabel("step")
+        plt.ylabel("held-out loss")
+        plt.legend()
+        plt.savefig(os.path.join(ROOT, "eval_loss.png"))
+        plt.cla()
 
     labels = [n for n in NAMES if n in dfs]
     colors = [c for n, c in zip(NAMES, COLORS) if n in dfs]
