@@ -9,13 +9,20 @@
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
+// a whole-tile (or split-K) 256^2 plan, as gp::plan_gemm would hand launch_big
+static gp::GemmPlan big_plan(int split) {
+  gp::GemmPlan p;
+  p.family = gp::FAM_BIG; p.bm = p.bn = BIG; p.sub = 4; p.split = split;
+  return p;
+}
+
 template <int EPI, bool F32, bool AK = true, bool BKM = true>
 float run(const GemmArgs& a, int reps, int split = 1) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i) { int rc = launch_big<AK, BKM, EPI, F32>(a, split, 0); CK((hipError_t)rc); }
+  for (int i = 0; i < 3; ++i) { int rc = launch_big<Variant<AK ? (BKM ? 0 : 1) : 2, EPI, F32>>(a, big_plan(split), 0); CK((hipError_t)rc); }
   CK(hipEventRecord(e0, 0));
-  for (int i = 0; i < reps; ++i) launch_big<AK, BKM, EPI, F32>(a, split, 0);
+  for (int i = 0; i < reps; ++i) launch_big<Variant<AK ? (BKM ? 0 : 1) : 2, EPI, F32>>(a, big_plan(split), 0);
   CK(hipEventRecord(e1, 0));
   CK(hipEventSynchronize(e1));
   float ms; CK(hipEventElapsedTime(&ms, e0, e1));
@@ -58,7 +65,7 @@ int main() {
   GemmArgs d{};
   d.layout = 1; d.M = M; d.N = 512; d.K = N; d.A = B; d.lda = N; d.B = Wb; d.ldb = 512; d.C = W32; d.ldc = 512;
   d.c_f32 = 1; d.alpha = 1.f; d.workspace = ws; d.ws_bytes = (long)64 << 20;
-  const int sp = big_split(1, M, 512, N);
+  const int sp = gp::big_split(1, M, 512, N, g_knobs);
   float td = run<EPI_STORE, true, true, false>(d, 10, sp);
   printf("dgrad [%d x 512 x %d] split %d %7.1f us (%6.1f TF/s)\n", M, N, sp, td, 2.0 * N * 512 * M / td * 1e-6);
   return 0;

@@ -171,8 +171,9 @@ int main() {
   {
     GemmArgs a{};
     a.layout = 0; a.M = M; a.N = 2048; a.K = 512; a.A = A; a.lda = 512; a.B = B; a.ldb = 512; a.C = C; a.ldc = 2048; a.alpha = 1.f;
-    Plan p128{128, 128, 64, 1};
-    printf("reg128 fc1 fwd main loop %6.2f us\n", timeit([&] { launch_t<128, 128, true, true, EPI_NONE, false>(a, p128, 0); }));
+    gp::GemmPlan p128;
+    p128.family = gp::FAM_REG; p128.bm = p128.bn = 128;
+    printf("reg128 fc1 fwd main loop %6.2f us\n", timeit([&] { launch_t<128, 128, Variant<0, EPI_NONE, false>>(a, p128, 0); }));
   }
   // wgrad (both MN-major), K = tokens
   sweep<false, false>("wgrad qkv", 1536, 512, 4096, A, B, C, 2);

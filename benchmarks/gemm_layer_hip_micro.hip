@@ -50,21 +50,23 @@ int main() {
     const double fl = 2.0 * M * N * K;
     GemmArgs a = args(N, K);
     for (int bm : {128, 64}) {
-      Plan p{bm, bm, 64, 1};
-      float t0 = timeit([&] { launch_sz<true, true, EPI_NONE, false>(a, p, 0); });
-      float t1 = timeit([&] { launch_sz<true, true, EPI_STORE, false>(a, p, 0); });
+      gp::GemmPlan p;  // the register-staged plan on bm^2 tiles (64^2 forward tiles: the LDS-DMA variant)
+      p.family = bm == 64 && g_knobs.dma_fwd64 ? gp::FAM_DMA64 : gp::FAM_REG;
+      p.bm = p.bn = bm;
+      float t0 = timeit([&] { launch_reg<Variant<0, EPI_NONE, false>>(a, p, 0); });
+      float t1 = timeit([&] { launch_reg<Variant<0, EPI_STORE, false>>(a, p, 0); });
       GemmArgs an = a; an.bias = nullptr;
-      float t1n = timeit([&] { launch_sz<true, true, EPI_STORE, false>(an, p, 0); });
+      float t1n = timeit([&] { launch_reg<Variant<0, EPI_STORE, false>>(an, p, 0); });
       GemmArgs af = a; af.C = R; af.c_f32 = 1;
-      float t1f = timeit([&] { launch_sz<true, true, EPI_STORE, true>(af, p, 0); });
-      float t2 = N == 2048 ? timeit([&] { launch_sz<true, true, EPI_GELU, false>(a, p, 0); }) : 0.f;
+      float t1f = timeit([&] { launch_reg<Variant<0, EPI_STORE, true>>(af, p, 0); });
+      float t2 = N == 2048 ? timeit([&] { launch_reg<Variant<0, EPI_GELU, false>>(a, p, 0); }) : 0.f;
       GemmArgs ar = a; ar.C = R; ar.c_f32 = 1; ar.aux = R; ar.ldaux = N;  // residual read from the output buffer
-      float t3 = N == 512 ? timeit([&] { launch_sz<true, true, EPI_RESID, true>(ar, p, 0); }) : 0.f;
+      float t3 = N == 512 ? timeit([&] { launch_reg<Variant<0, EPI_RESID, true>>(ar, p, 0); }) : 0.f;
       printf("[%d x %d x %d] %3d^2: main loop %6.2f us (%5.1f TF/s) | +bf16 store %6.2f (no bias %6.2f) | +f32 store %6.2f | "
              "+gelu %6.2f | +resid f32 %6.2f\n", M, N, K, bm, t0, fl / t0 * 1e-6, t1, t1n, t1f, t2, t3);
       for (int k : {64, 512}) {
         GemmArgs ak = args(N, k);
-        float t = timeit([&] { launch_sz<true, true, EPI_NONE, false>(ak, p, 0); });
+        float t = timeit([&] { launch_reg<Variant<0, EPI_NONE, false>>(ak, p, 0); });
         printf("    K=%5d main loop %6.2f us (%5.1f TF/s)\n", k, t, 2.0 * M * N * k / t * 1e-6);
       }
     }

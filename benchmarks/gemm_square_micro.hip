@@ -9,14 +9,21 @@
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
+// a whole-tile (or split-K) 256^2 plan, as gp::plan_gemm would hand launch_big
+static gp::GemmPlan big_plan(int split) {
+  gp::GemmPlan p;
+  p.family = gp::FAM_BIG; p.bm = p.bn = BIG; p.sub = 4; p.split = split;
+  return p;
+}
+
 template <bool AK, bool BKM, int EPI>
 float run(const GemmArgs& a, int reps) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i) { int rc = launch_big<AK, BKM, EPI, false>(a, 1, 0); if (rc) { printf("rc %d\n", rc); exit(1); } }
+  for (int i = 0; i < 3; ++i) { int rc = launch_big<Variant<AK ? 0 : 2, EPI, false>>(a, big_plan(1), 0); if (rc) { printf("rc %d\n", rc); exit(1); } }
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(e0, 0));
-  for (int i = 0; i < reps; ++i) launch_big<AK, BKM, EPI, false>(a, 1, 0);
+  for (int i = 0; i < reps; ++i) launch_big<Variant<AK ? 0 : 2, EPI, false>>(a, big_plan(1), 0);
   CK(hipEventRecord(e1, 0));
   CK(hipEventSynchronize(e1));
   float ms; CK(hipEventElapsedTime(&ms, e0, e1));

@@ -33,7 +33,7 @@ static float timeit(const std::function<void()>& f, int reps = 40) {
   return r[2];
 }
 
-// grid geometry exactly as launch_t computes it
+// grid geometry exactly as make_launch computes it
 struct Geo { int tm, tn, gm, kps, nb; };
 static Geo geo(const GemmArgs& a, int BM, int BN, int split) {
   Geo g;
@@ -74,10 +74,10 @@ static void run_reduce(const GemmArgs& a, int split) {
                      split, MN, (float*)a.C, a.ldc, a.N, 0.f);
 }
 
-struct Variant { std::string name; std::function<void(const GemmArgs&, int)> fn; };
+struct SweepVariant { std::string name; std::function<void(const GemmArgs&, int)> fn; };
 
 template <bool AK, bool BKM, int EPI, bool F32>
-std::vector<Variant> variants() {
+std::vector<SweepVariant> variants() {
   return {
       {"reg 128x128", run_reg<128, 128, AK, BKM, EPI, F32>},
       {"reg  64x64 ", run_reg<64, 64, AK, BKM, EPI, F32>},
@@ -136,7 +136,7 @@ int main() {
     if (s.layout == 2) ap.defer_reduce = 0;
     float tp = timeit([&] { dtc_gemm(&ap, 0); });
     printf("%s [%5d x %5d x %5d] production %7.2f us (%6.1f TF/s)\n", s.name, s.M, s.N, s.K, tp, fl / tp * 1e-6);
-    std::vector<Variant> vs;
+    std::vector<SweepVariant> vs;
     if (s.layout == 0 && s.epi == EPI_STORE) vs = variants<true, true, EPI_STORE, false>();
     if (s.layout == 0 && s.epi == EPI_GELU) vs = variants<true, true, EPI_GELU, false>();
     if (s.layout == 0 && s.epi == EPI_RESID) vs = variants<true, true, EPI_RESID, true>();

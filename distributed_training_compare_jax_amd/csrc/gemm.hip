@@ -24,6 +24,7 @@
 //    blocks sharing a weight panel share an L2).
 //  * Split-K (fp32 slabs + deterministic reduce) for the small wgrad grids.
 #include "common.h"
+#include "gemm_plan.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -2657,26 +2658,19 @@ gemm_dmaw_kernel(const bf16* __restrict__ A, long lda, const bf16* __restrict__ 
     }
 }
 
-struct Plan {
-  int bm, bn, bk, split;
-};
+// ============================================================================================
+// Host half.  dtc_gemm = validate, plan (gemm_plan.h: which family, tile, split-K and sub-variant, or which
+// refusal), launch from the plan.  The plan's (layout, epilogue, output) picks the template instance through
+// one table (with_variant); each family says next to its plan which combinations it instantiates (gp::*_has).
+// ============================================================================================
+static_assert(gp::EPI_STORE == EPI_STORE && gp::EPI_RESID == EPI_RESID && gp::EPI_GELU == EPI_GELU &&
+                  gp::EPI_DGELU == EPI_DGELU && gp::EPI_LMHEAD == EPI_LMHEAD &&
+                  gp::EPI_LMHEAD_EVAL == EPI_LMHEAD_EVAL && gp::BIG == BIG,
+              "gemm_plan.h mirrors these constants");
 
 // Record of the last launch: which kernel family ran, on what tile, with what split-K and sub-variant.
-// Written by the launch sites themselves (never recomputed from the plan functions, so it cannot drift
-// from what was launched); read by dtc_gemm_last_launch (tests assert the family a shape lands on).
-enum {
-  FAM_NONE = 0,
-  FAM_REG = 1,       // gemm_kernel, register-staged; sub = BK (32 / 64)
-  FAM_DMA64 = 2,     // gemm_dma_kernel 64^2 NT; sub = stages
-  FAM_DMAW = 3,      // gemm_dmaw_kernel; sub = stages, aux = wave grid WGM * 10 + WGN
-  FAM_BIG = 4,       // gemm8p_kernel; sub = CB (4 = 256^2, 3 = the 256 x 192 plan)
-  FAM_R8 = 5,        // gemm8r_kernel; sub = CB2, aux = n_split (columns on 256^2 tiles)
-  FAM_N8 = 6,        // gemm8n_kernel; sub = CB
-  FAM_PAIR = 7,      // gemm_pair_kernel; bm / bn = dgrad / weight-gradient tile, split = the weight gradient's
-  FAM_WGROUP = 8,    // gemm8p_group_kernel; split = tail split, sub = tail tiles, aux = all tiles
-  FAM_CE_DGRAD = 9,  // ce_dgrad256_kernel
-  FAM_LN = 10,       // gemm_dmaw_kernel with a LayerNorm epilogue; sub = 1 backward, 0 forward
-};
+// Written by the launch sites themselves from their template constants (never copied from the plan, so it
+// cannot drift from what was launched); read by dtc_gemm_last_launch (tests assert the family a shape lands on).
 struct LastLaunch {
   int family, bm, bn, split, sub, aux, layout, epi;
 };
@@ -2685,200 +2679,8 @@ inline void note_launch(int family, int bm, int bn, int split, int sub, int aux,
   g_last = LastLaunch{family, bm, bn, split, sub, aux, layout, epi};
 }
 
-// LDS-DMA variant of the 64x64 forward-layout tiles (measured fc2/out_proj fwd 22 -> 18.6 us; the
-// dgrad / wgrad layouts and the 128x128 tiles measured slower or equal on it and stay register-staged).
-// DTC_GEMM_DMA=0: register-staged everywhere (diagnostic)
-inline bool gemm_dma_fwd64() {
-  static const bool m = [] { const char* v = getenv("DTC_GEMM_DMA"); return v ? atoi(v) != 0 : true; }();
-  return m;
-}
-
-// allow_split: 1 = small-grid split (wgrad), 2 = huge-K only (dgrad through the lm_head)
-Plan make_plan(int M, int N, int K, int allow_split) {
-  Plan p{128, 128, 64, 1};
-  if (K % 64) {  // K a multiple of 32 only (e.g. a TP shard of d_model=768): BK=32, small tiles
-    p.bm = p.bn = 64;
-    p.bk = 32;
-    return p;
-  }
-  const int nk = K / 64;
-  const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-  if (allow_split && K >= 8192 && t128 >= 32) {  // e.g. dH = dlogits . W_lm (K = vocab)
-    p.split = (int)std::max(1L, std::min((long)nk / 64, (512 + t128 - 1) / t128));
-    return p;
-  }
-  // weight gradients: 128^2 tiles + split-K (A/B: 5.99 vs 6.05 ms on 64^2 tiles)
-  if (allow_split == 1 && t128 < 256) {
-    static const int target = [] { const char* v = getenv("DTC_WGRAD_BLOCKS"); return v ? atoi(v) : 256; }();
-    while (t128 * p.split < target && nk / (p.split * 2) >= 8) p.split *= 2;
-    return p;
-  }
-  if (t128 >= 256) return p;
-  {
-    p.bm = p.bn = 64;
-    const long t64 = (long)((M + 63) / 64) * ((N + 63) / 64);
-    if (allow_split == 1)
-    {
-      // weight gradients run on the backward side stream next to the dgrad chain: a grid that
-      // fills every CU starves the critical path, so their split-K targets DTC_WGRAD_BLOCKS blocks
-      static const int target = [] { const char* v = getenv("DTC_WGRAD_BLOCKS"); return v ? atoi(v) : 512; }();
-      while (t64 * p.split < target && nk / (p.split * 2) >= 4) p.split *= 2;
-    }
-  }
-  return p;
-}
-
-// Tile-group height for grids with many N-tiles (> 16): groups of gm M-tiles sweep the N-tiles, so the
-// blocks an XCD runs at once share gm A panels (L2-resident) and stream the B panels.  Was gm = tiles_m
-// (every M-tile of one N-tile in a row): an XCD then re-fetched all of A for each N-tile -- the GPT-2
-// small fc1 forward / fc2 dgrad (24 N-tiles of 128) pulled 408 MB per call through L2 and the lm_head
-// forward 3.5 GB (rocprofv3 FETCH_SIZE, profiles/r3_gpt2_small_pmc_final.md).  DTC_WIDE_GM: the height
-// (0 = the old tiles_m).
-inline int wide_gm(int tiles_m) {
-  static const int g = [] { const char* v = getenv("DTC_WIDE_GM"); return v ? atoi(v) : 3; }();
-  return g > 0 ? std::min(tiles_m, g) : tiles_m;
-}
-
-// exact byte extent of an operand (rows x K if K-major, K x rows if MN-major) for the buffer range check
-inline int operand_bytes(bool kmajor, int rows, int K, long ld) {
-  long n = kmajor ? ((long)(rows - 1) * ld + K) : ((long)(K - 1) * ld + rows);
-  return (int)std::min(n * 2, (long)0x7FFFFFF0);
-}
-
-// Plan a register-staged launch of problem `a` with tile BMxBN (grid geometry, operand extents,
-// epilogue) — shared by the single and the paired launch paths.
-template <int BM, int BN, bool AK, bool BKM>
-GemmLaunch make_launch(const GemmArgs& a, const Plan& p) {
-  GemmLaunch g;
-  Epi& e = g.e;
-  e = Epi{};
-  e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
-  e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
-  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg;
-  e.colsum = a.colsum;
-  g.tiles_m = (a.M + BM - 1) / BM;
-  g.tiles_n = (a.N + BN - 1) / BN;
-  e.nparts = g.tiles_n * 2;
-  const int nk = a.K / p.bk;
-  g.kps = ((nk + p.split - 1) / p.split) * p.bk;
-  const int ntiles = g.tiles_m * g.tiles_n;
-  g.gm = wide_gm(g.tiles_m);
-  if (g.tiles_n <= 16) g.gm = std::max(1, std::min(g.tiles_m, (ntiles / 8 + g.tiles_n - 1) / g.tiles_n));
-  g.split = p.split;
-  g.nblocks = ntiles * p.split;
-  g.A = (const bf16*)a.A; g.lda = a.lda; g.a_bytes = operand_bytes(AK, a.M, a.K, a.lda);
-  g.B = (const bf16*)a.B; g.ldb = a.ldb; g.b_bytes = operand_bytes(BKM, a.N, a.K, a.ldb);
-  g.M = a.M; g.N = a.N; g.K = a.K;
-  g.slab = (float*)a.workspace;
-  return g;
-}
-
-template <int BM, int BN, bool AK, bool BKM, int EPI, bool OUTF32>
-int launch_t(const GemmArgs& a, const Plan& p, hipStream_t st) {
-  Epi e{};
-  e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
-  e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
-  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg;
-  e.colsum = a.colsum;
-  int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-  e.nparts = tiles_n * 2;
-  const int nk = a.K / p.bk;
-  const int kps = ((nk + p.split - 1) / p.split) * p.bk;
-  const int ntiles = tiles_m * tiles_n;
-  // per-XCD share of tiles = ntiles*split/8: with few N-tiles make each XCD own whole M-row groups
-  int gm = wide_gm(tiles_m);
-  if (tiles_n <= 16) gm = std::max(1, std::min(tiles_m, (ntiles / 8 + tiles_n - 1) / tiles_n));
-  dim3 grid(ntiles * p.split);
-  const int ab = operand_bytes(AK, a.M, a.K, a.lda), bb = operand_bytes(BKM, a.N, a.K, a.ldb);
-  if constexpr (BM == 64 && AK && BKM) {
-    if (p.bk == 64 && gemm_dma_fwd64()) {
-      hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, 4, AK, BKM, EPI, OUTF32>), grid, dim3(NT), 0, st, (const bf16*)a.A,
-                         a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm, p.split, kps,
-                         (float*)a.workspace, e);
-      DTC_CHECK_LAUNCH();
-      note_launch(FAM_DMA64, BM, BN, p.split, 4, 0, a.layout, EPI);
-      if (p.split > 1 && !a.defer_reduce) {
-        long MN = (long)a.M * a.N;
-        int blocks = (int)((MN / 4 + 255) / 256);
-        hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, st, (const float*)a.workspace, p.split, MN,
-                           (float*)a.C, a.ldc, a.N, a.beta);
-        DTC_CHECK_LAUNCH();
-      }
-      return 0;
-    }
-  }
-  if (p.bk == 32) {
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, 32, AK, BKM, EPI, OUTF32>), grid, dim3(NT), 0, st, (const bf16*)a.A, a.lda,
-                       ab, (const bf16*)a.B, a.ldb, bb, a.M, a.N, a.K, tiles_m, tiles_n, gm, p.split, kps,
-                       (float*)a.workspace, e);
-    note_launch(FAM_REG, BM, BN, p.split, 32, 0, a.layout, EPI);
-  } else if (p.bk == 64) {
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, 64, AK, BKM, EPI, OUTF32>), grid, dim3(NT), 0, st, (const bf16*)a.A, a.lda,
-                       ab, (const bf16*)a.B, a.ldb, bb, a.M, a.N, a.K, tiles_m, tiles_n, gm, p.split, kps,
-                       (float*)a.workspace, e);
-    note_launch(FAM_REG, BM, BN, p.split, 64, 0, a.layout, EPI);
-  } else
-    return 1007;
-  DTC_CHECK_LAUNCH();
-  if (p.split > 1 && !a.defer_reduce) {
-    long MN = (long)a.M * a.N;
-    int blocks = (int)((MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, st, (const float*)a.workspace, p.split, MN,
-                       (float*)a.C, a.ldc, a.N, a.beta);
-    DTC_CHECK_LAUNCH();
-  }
-  return 0;
-}
-
-template <bool AK, bool BKM, int EPI, bool OUTF32>
-int launch_sz(const GemmArgs& a, const Plan& p, hipStream_t st) {
-  if (p.bm == 128) return launch_t<128, 128, AK, BKM, EPI, OUTF32>(a, p, st);
-  return launch_t<64, 64, AK, BKM, EPI, OUTF32>(a, p, st);
-}
-
-
-// The 256^2 kernel pays on lm_head-sized problems.  Returns the split-K factor (0 = use the
-// 128/64 kernels).  layout 0 (fwd): whole tiles; layout 1 (dgrad through the lm_head, K = vocab):
-// split so ~256 blocks run (so does layout 0 at K >= 16384: the same dgrad as an NT GEMM on a
-// transposed lm_head weight, ~25% faster main loop with both operands K-major); layout 2 (wgrad): no split (a 103 MB fp32 output; extra slab passes
-// cost more than the last partial wave of tiles).
-// DTC_WGRAD_CS256=0: bias gradients of the split-K 256^2 weight gradients as a separate column sum
-static int g_wgrad_cs256 = [] { const char* v = getenv("DTC_WGRAD_CS256"); return v ? atoi(v) : 1; }();
-static int g_wgrad256 = [] { const char* v = getenv("DTC_WGRAD256"); return v ? atoi(v) : 1; }();
-
-int big_split(int layout, int M, int N, int K) {
-  // DTC_GEMM256: bit mask of layouts allowed to use it (1 fwd, 2 dgrad, 4 wgrad; default all)
-  static const int enabled = [] { const char* v = getenv("DTC_GEMM256"); return v ? atoi(v) : 7; }();
-  if (!(enabled & (1 << layout)) || K % 64) return 0;
-  if (layout != 0 && N % 8) return 0;              // MN-major B extent (dgrad / wgrad)
-  if (layout == 2 && M % 8) return 0;              // MN-major A extent (wgrad)
-  static const int min_tiles = [] { const char* v = getenv("DTC_BIG_MIN_TILES"); return v ? atoi(v) : 512; }();
-  const long t = (long)((M + BIG - 1) / BIG) * ((N + BIG - 1) / BIG);
-  if (layout == 2) {
-    if (t >= 256 && K >= 1024) return 1;
-    // DTC_WGRAD256=1 (default; in-step 14.30 -> 14.23 ms): layer weight gradients (K = tokens, a few dozen 256^2 tiles) split-K across
-    // ~256 blocks of >= 8 K-steps on this kernel, fp32 slabs summed by the caller's reducer
-    // K >= 8192 tokens: at the reference model's 4096 the split pieces are 4-8 K-steps and the grid half
-    // empty (whole step 4.65 -> 5.04 ms with it, profiles/r3_ab_ref_regress.log)
-    if (!g_wgrad256 || t < 8 || K < 8192) return 0;
-    int split = (int)std::max(1L, 256 / t);
-    while (split > 1 && (K / 64) / split < 8) --split;
-    // fp32 slabs of one problem <= 96 MB (a layer's four weight gradients share the reducer's window)
-    while (split > 1 && (long)split * M * N * 4 > (96L << 20)) --split;
-    return split > 1 ? split : 0;
-  }
-  // ordinary K: whole tiles, when there are enough of them, or when the last round of 256^2 tiles is
-  // nearly empty anyway (GPT-2 small qkv forward: 288 tiles = 1.125 rounds, 54.7 -> 47.7 us;
-  // fc1's 384 = 1.5 rounds stays on the 128^2 kernel: 76 vs 85 us, profiles/r3_gemm_bench_gpt2s*.log)
-  static const int tail_ok = [] { const char* v = getenv("DTC_BIG_TAIL"); return v ? atoi(v) : 64; }();
-  if (K < 16384) return (t >= min_tiles || (layout == 0 && t >= 256 && t % 256 <= tail_ok)) ? 1 : 0;
-  if (t > 256) return 0;                           // dgrad through the vocab (NN, or NT on W^T): split-K
-  int split = (int)std::max(1L, 256 / t);
-  while (split > 1 && (K / 64) / split < 8) --split;
-  return split;
-}
-
-inline int big_kps(int K, int split) { return ((K / 64 + split - 1) / split) * 64; }
+// every environment switch of the dispatch (gemm_plan.h), read once at load; dtc_gemm_set_* write into it
+static gp::Knobs g_knobs = gp::knobs_from_env();
 
 // compute units of the current device (one-block-per-CU persistent grids)
 static int cu_count() {
@@ -2890,210 +2692,295 @@ static int cu_count() {
   return n;
 }
 
-// default on: GPT-2 small lm_head dgrad 553 -> 502 us, step 11.01-11.04 vs 11.04-11.09 ms
-// (profiles/r4_ab_big_cb3.log)
-static int g_big_cb3 = [] { const char* v = getenv("DTC_BIG_CB3"); return v ? atoi(v) : 1; }();
-template <bool AK, bool BKM, int EPI, bool OUTF32>
-int launch_big(const GemmArgs& a, int split, hipStream_t st) {
+inline gp::GemmPlan plan_of(const GemmArgs& a) {
+  const gp::Problem q{a.layout, a.M, a.N, a.K, a.epi, a.c_f32 != 0, a.bias != nullptr, a.colsum != nullptr,
+                      a.alpha == 1.f && a.beta == 0.f, a.part_arg && a.part && a.label_out && a.labels, a.ws_bytes};
+  return gp::plan_gemm(q, cu_count(), g_knobs);
+}
+// dtc_gemm's first two steps: the code it returns without launching, or -1 and the plan to launch
+inline int validate_and_plan(const GemmArgs& a, gp::GemmPlan& p) {
+  if (a.K % 32 != 0) return 1001;               // K must be a multiple of 32 (BK = 64, or 32)
+  if (a.lda % 8 || a.ldb % 8 || a.ldc % 4) return 1002;  // 16-B row alignment
+  if (a.M <= 0 || a.N <= 0) return 0;
+  p = plan_of(a);
+  return p.err ? p.err : -1;
+}
+// the plan of a bare problem, as the queries ask for it: no bias, unit alpha / beta, ample workspace
+inline gp::GemmPlan plan_query(int layout, int M, int N, int K, int epi, bool f32, bool has_colsum) {
+  return gp::plan_gemm(gp::Problem{layout, M, N, K, epi, f32, false, has_colsum, true, true, LONG_MAX}, cu_count(), g_knobs);
+}
+
+// ---- tile-group heights ----------------------------------------------------------------------------------
+// Groups of gm M-tiles sweep the N-tiles, so the blocks an XCD runs at once share gm A panels (L2-resident)
+// and stream the B panels.  Grids with many N-tiles (> 16) take DTC_WIDE_GM (0 = the old tiles_m: every
+// M-tile of one N-tile in a row, where an XCD re-fetched all of A for each N-tile -- the GPT-2 small fc1
+// forward / fc2 dgrad (24 N-tiles of 128) pulled 408 MB per call through L2 and the lm_head forward 3.5 GB,
+// rocprofv3 FETCH_SIZE, profiles/r3_gpt2_small_pmc_final.md).
+inline int wide_gm(int tiles_m) { return g_knobs.wide_gm > 0 ? std::min(tiles_m, g_knobs.wide_gm) : tiles_m; }
+// few N-tiles, many small blocks per CU: an XCD's share of the tiles (ntiles / 8) in whole M-row groups
+inline int gm_xcd_share(int tiles_m, int tiles_n) {
+  if (tiles_n > 16) return wide_gm(tiles_m);
+  return std::max(1, std::min(tiles_m, (tiles_m * tiles_n / 8 + tiles_n - 1) / tiles_n));
+}
+// one block per CU: a group is sized to the ~32 blocks an XCD runs at once, so the N-tiles sharing an A panel
+// run together on one L2 (a group spanning a whole XCD run -- 74 tiles of the lm_head weight gradient -- left
+// 2 of its 3 N-tiles re-fetching their A panel from HBM: 2x FETCH_SIZE, profiles/r3_gemm8p.md)
+inline int gm_round32(int tiles_m, int tiles_n) { return std::max(1, std::min(tiles_m, 32 / tiles_n)); }
+// gemm8n: an XCD's ~32 concurrent tiles = 8 M-tiles x 4 N-tiles (A panel and B panel both shared)
+inline int gm_n8(int tiles_m, int tiles_n) { return tiles_n <= 4 ? gm_round32(tiles_m, tiles_n) : std::min(tiles_m, 8); }
+
+// exact byte extent of an operand (rows x K if K-major, K x rows if MN-major) for the buffer range check
+inline int operand_bytes(bool kmajor, int rows, int K, long ld) {
+  long n = kmajor ? ((long)(rows - 1) * ld + K) : ((long)(K - 1) * ld + rows);
+  return (int)std::min(n * 2, (long)0x7FFFFFF0);
+}
+
+// the epilogue arguments of a problem; nparts = row-statistics parts per row (lm_head epilogues)
+inline Epi make_epi(const GemmArgs& a, int nparts) {
   Epi e{};
   e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
   e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
   e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg;
-  e.colsum = a.colsum;  // fused bias gradient (gemm8p_kernel, layout TN only)
-  const int tiles_m = (a.M + BIG - 1) / BIG, tiles_n = (a.N + BIG - 1) / BIG;
-  e.nparts = tiles_n * 4;
-  const int ntiles = tiles_m * tiles_n;
-  // tile order: groups of gm M-tiles sweep all N-tiles.  With few N-tiles a group is sized to the
-  // ~32 blocks an XCD runs at once, so the N-tiles sharing an A panel run together on one L2 (a group
-  // spanning a whole XCD run -- 74 tiles of the lm_head weight gradient -- left 2 of its 3 N-tiles
-  // re-fetching their A panel from HBM: 2x FETCH_SIZE, profiles/r3_gemm8p.md)
-  int gm = wide_gm(tiles_m);
-  if (tiles_n <= 16) gm = std::max(1, std::min(tiles_m, 32 / tiles_n));
-  const int kps = big_kps(a.K, split);
-  if (split > 1 && (a.ws_bytes < (long)split * a.M * a.N * 4 || a.N % 4)) return 1005;
-  // DTC_BIG_CB3: split-K problems whose 256^2 grid leaves CUs idle (the GPT-2 small lm_head dgrad: 96 tiles
-  // x split 2 = 192 blocks) run 256 x 192 tiles when that grid is exactly one block per CU (128 x 2 = 256)
-  const int cb3 = g_big_cb3;
-  bool done = false;
-  if constexpr (EPI == EPI_STORE && OUTF32) {
-    const int tn3 = a.N / 192;
-    if (cb3 && split > 1 && a.N % 192 == 0 && ntiles * split < cu_count() && tiles_m * tn3 * split == cu_count()) {
-      const int gm3 = std::max(1, std::min(tiles_m, 32 / tn3));
-      hipLaunchKernelGGL((gemm8p_kernel<AK, BKM, EPI, OUTF32, 3>), dim3(tiles_m * tn3 * split), dim3(NT2), 0, st,
-                         (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tn3, gm3, split,
-                         kps, (float*)a.workspace, e);
-      DTC_CHECK_LAUNCH();
-      note_launch(FAM_BIG, BIG, 192, split, 3, 0, a.layout, EPI);
-      done = true;
-    }
-  }
-  if (!done) {
-    hipLaunchKernelGGL((gemm8p_kernel<AK, BKM, EPI, OUTF32>), dim3(ntiles * split), dim3(NT2), 0, st,
-                       (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm, split,
-                       kps, (float*)a.workspace, e);
-    DTC_CHECK_LAUNCH();
-    note_launch(FAM_BIG, BIG, BIG, split, 4, 0, a.layout, EPI);
-  }
+  e.colsum = a.colsum;  // fused bias gradient (layout TN only)
+  e.nparts = nparts;
+  return e;
+}
+
+// sums the split-K slabs into C unless the caller's batched reducer will (defer_reduce)
+inline int finish_splitk(const GemmArgs& a, int split, hipStream_t st) {
   if (split > 1 && !a.defer_reduce) {
-    long MN = (long)a.M * a.N;
-    int blocks = (int)((MN / 4 + 255) / 256);
-    hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, st, (const float*)a.workspace, split, MN,
-                       (float*)a.C, a.ldc, a.N, a.beta);
+    const long MN = (long)a.M * a.N;
+    hipLaunchKernelGGL(splitk_reduce, dim3((int)((MN / 4 + 255) / 256)), dim3(256), 0, st, (const float*)a.workspace, split,
+                       MN, (float*)a.C, a.ldc, a.N, a.beta);
     DTC_CHECK_LAUNCH();
   }
   return 0;
 }
 
-// ---- gemm8r plans (layer GEMMs on 256-row tiles of two widths, one launch) ---------------------------
-// DTC_GEMM8R: 1 (default) = use the plan for NT problems (forwards, dgrads on transposed weights) with a bf16
-// staged epilogue (plain + bias, GELU pair, dGELU) whose 256^2 grid is not whole rounds; 2 = also fp32
-// outputs (measured slower: out_proj f32 21 -> 29 us); 4 = also NN problems (dgrads on the row-major weight:
-// the fc2 dgrad + dGELU); 0 = off.  HBM-cold, GPT-2 small (profiles/r5_gemm8r.md):
-// qkv fwd 44.5 -> 41.6 us, fc1 fwd + GELU 67.3 -> 54.9, fc2 NT dgrad + dGELU 73.7 -> 61.3; step 10.89 -> 10.74 ms
-// NN added (default 5): fc2 dgrad + dGELU on the row-major weight 74.3 -> 62.3 us cold, step 10.84 -> 10.74 ms
-// (profiles/r5_gemm8r.md), level with the NT form on a transposed copy (DTC_DGRAD_NT_FC2=1: 10.76 ms)
-static int g_r8_mask = [] { const char* v = getenv("DTC_GEMM8R"); return v ? atoi(v) : 5; }();
-// DTC_R8_ILV: interleaved gemm8r block order (r8_block); A/B switch, set at run time by dtc_gemm_set_r8_ilv
-static int g_r8_ilv = [] { const char* v = getenv("DTC_R8_ILV"); return v ? atoi(v) : 1; }();
-
-struct R8Plan {
-  int n_split = -1, cb2 = 0;
+// ---- the variant table -----------------------------------------------------------------------------------
+template <int L, int E, bool F>
+struct Variant {
+  static constexpr int layout = L, epi = E;
+  static constexpr bool f32 = F, AK = L != 2, BKM = L == 0;  // operand A / B K-major
 };
 
-static R8Plan r8_plan(int layout, int M, int N, int K, int epi, bool f32) {
-  R8Plan r;
-  if (!g_r8_mask || !(layout == 0 || (layout == 1 && (g_r8_mask & 4))) || M % BIG || N % 64 || K % 64 || K < 256 ||
-      K > 4096 || N > 16384)
-    return r;
-  if (!(epi == EPI_STORE || epi == EPI_GELU || epi == EPI_DGELU)) return r;
-  if (f32 && (epi != EPI_STORE || !(g_r8_mask & 2))) return r;
-  const int tm = M / BIG, q = N / BIG, cus = cu_count();
-  if ((long)tm * q % cus == 0 && q > 0 && N % BIG == 0) return r;  // whole rounds of 256^2 tiles: launch_big
-  int c1 = q;
-  while (c1 > 0 && ((long)tm * c1) % cus) --c1;  // whole rounds of 256^2 tiles
-  const int u = (N - BIG * c1) / 64;
-  int best = 0;
-  long best_cost = 0;
-  for (int cb : {4, 2, 1}) {
-    if (u % cb) continue;
-    const long blocks = (long)tm * (u / cb);
-    const long cost = ((blocks + cus - 1) / cus) * cb;  // rounds x tile width
-    if (!best || cost < best_cost) {
-      best = cb;
-      best_cost = cost;
+// Calls fn(Variant<layout, epi, f32>{}) for the run-time triple: the one place that maps it to template
+// constants.  fn is instantiated for every entry, so it guards each family's launcher with `if constexpr` on
+// that family's gp::*_has predicate (see launch) and only those kernels exist.
+template <int L, class Fn>
+int with_variant_of(int epi, bool f32, Fn&& fn) {
+  switch (epi) {
+    case EPI_STORE: return f32 ? fn(Variant<L, EPI_STORE, true>{}) : fn(Variant<L, EPI_STORE, false>{});
+    case EPI_RESID: return f32 ? fn(Variant<L, EPI_RESID, true>{}) : fn(Variant<L, EPI_RESID, false>{});
+    case EPI_GELU: return f32 ? fn(Variant<L, EPI_GELU, true>{}) : fn(Variant<L, EPI_GELU, false>{});
+    case EPI_DGELU: return f32 ? fn(Variant<L, EPI_DGELU, true>{}) : fn(Variant<L, EPI_DGELU, false>{});
+    case EPI_LMHEAD: return f32 ? fn(Variant<L, EPI_LMHEAD, true>{}) : fn(Variant<L, EPI_LMHEAD, false>{});
+    case EPI_LMHEAD_EVAL: return f32 ? fn(Variant<L, EPI_LMHEAD_EVAL, true>{}) : fn(Variant<L, EPI_LMHEAD_EVAL, false>{});
+  }
+  return 1003;
+}
+template <class Fn>
+int with_variant(int layout, int epi, bool f32, Fn&& fn) {
+  switch (layout) {
+    case 0: return with_variant_of<0>(epi, f32, fn);
+    case 1: return with_variant_of<1>(epi, f32, fn);
+    case 2: return with_variant_of<2>(epi, f32, fn);
+  }
+  return 1006;
+}
+constexpr int NOT_INSTANTIATED = 1101;  // a plan and its family's *_has predicate disagree
+
+// ---- register-staged kernels (gemm_kernel, gemm_dma_kernel) ------------------------------------------------
+// Grid geometry, operand extents and epilogue of problem `a` on BM x BN tiles — shared by the single and the
+// paired launch paths.
+template <int BM, int BN, bool AK, bool BKM>
+GemmLaunch make_launch(const GemmArgs& a, const gp::GemmPlan& p) {
+  GemmLaunch g;
+  g.tiles_m = (a.M + BM - 1) / BM;
+  g.tiles_n = (a.N + BN - 1) / BN;
+  g.e = make_epi(a, g.tiles_n * 2);
+  const int nk = a.K / p.bk;
+  g.kps = ((nk + p.split - 1) / p.split) * p.bk;
+  g.gm = gm_xcd_share(g.tiles_m, g.tiles_n);
+  g.split = p.split;
+  g.nblocks = g.tiles_m * g.tiles_n * p.split;
+  g.A = (const bf16*)a.A; g.lda = a.lda; g.a_bytes = operand_bytes(AK, a.M, a.K, a.lda);
+  g.B = (const bf16*)a.B; g.ldb = a.ldb; g.b_bytes = operand_bytes(BKM, a.N, a.K, a.ldb);
+  g.M = a.M; g.N = a.N; g.K = a.K;
+  g.slab = (float*)a.workspace;
+  return g;
+}
+
+// LDS-DMA variant of the 64x64 forward-layout tiles (measured fc2/out_proj fwd 22 -> 18.6 us; the
+// dgrad / wgrad layouts and the 128x128 tiles measured slower or equal on it and stay register-staged).
+template <int BM, int BN, class V>
+int launch_t(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  const GemmLaunch g = make_launch<BM, BN, V::AK, V::BKM>(a, p);
+  const dim3 grid(g.nblocks);
+  if constexpr (BM == 64 && V::AK && V::BKM) {
+    if (p.family == gp::FAM_DMA64) {
+      hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, 4, V::AK, V::BKM, V::epi, V::f32>), grid, dim3(NT), 0, st, g.A, g.lda, g.B,
+                         g.ldb, g.M, g.N, g.K, g.tiles_m, g.tiles_n, g.gm, g.split, g.kps, g.slab, g.e);
+      DTC_CHECK_LAUNCH();
+      note_launch(gp::FAM_DMA64, BM, BN, g.split, 4, 0, a.layout, V::epi);
+      return finish_splitk(a, g.split, st);
     }
   }
-  if (!best) return r;
-  r.n_split = BIG * c1;
-  r.cb2 = best;
+  if (p.bk == 32) {
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, 32, V::AK, V::BKM, V::epi, V::f32>), grid, dim3(NT), 0, st, g.A, g.lda, g.a_bytes,
+                       g.B, g.ldb, g.b_bytes, g.M, g.N, g.K, g.tiles_m, g.tiles_n, g.gm, g.split, g.kps, g.slab, g.e);
+    note_launch(gp::FAM_REG, BM, BN, g.split, 32, 0, a.layout, V::epi);
+  } else if (p.bk == 64) {
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, 64, V::AK, V::BKM, V::epi, V::f32>), grid, dim3(NT), 0, st, g.A, g.lda, g.a_bytes,
+                       g.B, g.ldb, g.b_bytes, g.M, g.N, g.K, g.tiles_m, g.tiles_n, g.gm, g.split, g.kps, g.slab, g.e);
+    note_launch(gp::FAM_REG, BM, BN, g.split, 64, 0, a.layout, V::epi);
+  } else
+    return 1007;
+  DTC_CHECK_LAUNCH();
+  return finish_splitk(a, g.split, st);
+}
+
+template <class V>
+int launch_reg(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  if constexpr (gp::reg_has_tile64(V::epi))
+    if (p.bm == 64) return launch_t<64, 64, V>(a, p, st);
+  return launch_t<128, 128, V>(a, p, st);
+}
+
+// ---- 256^2 tiles (gemm8p_kernel) ---------------------------------------------------------------------------
+inline int big_kps(int K, int split) { return ((K / 64 + split - 1) / split) * 64; }
+
+template <class V>
+int launch_big(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  const int tiles_m = (a.M + BIG - 1) / BIG, tiles_n = (a.N + BIG - 1) / BIG, split = p.split;
+  const Epi e = make_epi(a, tiles_n * 4);
+  const int kps = big_kps(a.K, split);
+  if constexpr (V::epi == EPI_STORE && V::f32) {
+    if (p.sub == 3) {  // the 256 x 192 split-K plan
+      const int tn3 = a.N / 192;
+      hipLaunchKernelGGL((gemm8p_kernel<V::AK, V::BKM, V::epi, V::f32, 3>), dim3(tiles_m * tn3 * split), dim3(NT2), 0, st,
+                         (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tn3,
+                         gm_round32(tiles_m, tn3), split, kps, (float*)a.workspace, e);
+      DTC_CHECK_LAUNCH();
+      note_launch(gp::FAM_BIG, BIG, 192, split, 3, 0, a.layout, V::epi);
+      return finish_splitk(a, split, st);
+    }
+  }
+  const int gm = tiles_n <= 16 ? gm_round32(tiles_m, tiles_n) : wide_gm(tiles_m);
+  hipLaunchKernelGGL((gemm8p_kernel<V::AK, V::BKM, V::epi, V::f32>), dim3(tiles_m * tiles_n * split), dim3(NT2), 0, st,
+                     (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm, split,
+                     kps, (float*)a.workspace, e);
+  DTC_CHECK_LAUNCH();
+  note_launch(gp::FAM_BIG, BIG, BIG, split, 4, 0, a.layout, V::epi);
+  return finish_splitk(a, split, st);
+}
+
+// ---- gemm8r_kernel: p.sub = CB2, p.aux = the columns on 256^2 tiles ----------------------------------------
+template <class V, int CB2>
+int launch_r8_cb(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  const Epi e = make_epi(a, 0);
+  R8Args r;
+  r.A = (const bf16*)a.A; r.lda = a.lda; r.B = (const bf16*)a.B; r.ldb = a.ldb;
+  r.M = a.M; r.N = a.N; r.K = a.K; r.n_split = p.aux;
+  r.tm = a.M / BIG;
+  r.tn1 = r.n_split / BIG;
+  r.nb1 = r.tm * r.tn1;
+  r.gm1 = r.tn1 > 0 ? gm_round32(r.tm, r.tn1) : 1;
+  r.tn2 = (a.N - r.n_split) / (64 * CB2);
+  r.gm2 = gm_round32(r.tm, std::max(1, r.tn2));
+  r.ilv = g_knobs.r8_ilv && r.nb1 >= 2 && r.tm * r.tn2 >= 2;
+  const int grid = r.nb1 + r.tm * r.tn2;
+  hipLaunchKernelGGL((gemm8r_kernel<V::AK, V::BKM, V::epi, V::f32, CB2>), dim3(grid), dim3(NT2), 0, st, r, e);
+  DTC_CHECK_LAUNCH();
+  note_launch(gp::FAM_R8, BIG, 64 * CB2, 1, CB2, r.n_split, a.layout, V::epi);
+  return 0;
+}
+
+template <class V>
+int launch_r8(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  if (p.sub == 4) return launch_r8_cb<V, 4>(a, p, st);
+  if (p.sub == 2) return launch_r8_cb<V, 2>(a, p, st);
+  return launch_r8_cb<V, 1>(a, p, st);
+}
+
+// ---- gemm8n_kernel: p.sub = CB -----------------------------------------------------------------------------
+template <class V, int CB>
+int launch_n8_cb(const GemmArgs& a, hipStream_t st) {
+  const Epi e = make_epi(a, 0);
+  const int tiles_m = (a.M + 127) / 128, tiles_n = a.N / (64 * CB);
+  constexpr int NS = CB == 3 ? 4 : 3;
+  const int grid = std::min(tiles_m * tiles_n, cu_count());  // persistent: one block per CU
+  hipLaunchKernelGGL((gemm8n_kernel<CB, NS, V::AK, V::BKM, V::epi, V::f32>), dim3(grid), dim3(NT2), 0, st,
+                     (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n,
+                     gm_n8(tiles_m, tiles_n), e);
+  DTC_CHECK_LAUNCH();
+  note_launch(gp::FAM_N8, 128, 64 * CB, 1, CB, 0, a.layout, V::epi);
+  return 0;
+}
+
+template <class V>
+int launch_n8(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  return p.sub == 3 ? launch_n8_cb<V, 3>(a, st) : launch_n8_cb<V, 4>(a, st);
+}
+
+// ---- gemm_dmaw_kernel: the plan's tile names the 8-wave config ---------------------------------------------
+template <class V, int CFG>
+int launch_w(const GemmArgs& a, int split, hipStream_t st) {
+  constexpr gp::WTile T = gp::W_TILES[CFG];
+  const int tiles_m = (a.M + T.bm - 1) / T.bm, tiles_n = (a.N + T.bn - 1) / T.bn;
+  const Epi e = make_epi(a, tiles_n * T.wgn);
+  const int nk = a.K / 64;
+  const int kps = ((nk + split - 1) / split) * 64;
+  hipLaunchKernelGGL((gemm_dmaw_kernel<T.bm, T.bn, T.stages, T.wgm, T.wgn, V::AK, V::BKM, V::epi, V::f32>),
+                     dim3(tiles_m * tiles_n * split), dim3(64 * T.wgm * T.wgn), 0, st, (const bf16*)a.A, a.lda,
+                     (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm_xcd_share(tiles_m, tiles_n), split, kps,
+                     (float*)a.workspace, e);
+  DTC_CHECK_LAUNCH();
+  note_launch(gp::FAM_DMAW, T.bm, T.bn, split, T.stages, T.wgm * 10 + T.wgn, a.layout, V::epi);
+  return finish_splitk(a, split, st);
+}
+
+template <class V, int CFG>
+int launch_w_if(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  if constexpr (gp::dmaw_cfg_has(CFG, V::layout, V::epi, V::f32))
+    if (p.bm == gp::W_TILES[CFG].bm && p.bn == gp::W_TILES[CFG].bn) return launch_w<V, CFG>(a, p.split, st);
+  return NOT_INSTANTIATED;
+}
+
+template <class V>
+int launch_dmaw(const GemmArgs& a, const gp::GemmPlan& p, hipStream_t st) {
+  int r = launch_w_if<V, gp::W_256x128>(a, p, st);
+  if (r == NOT_INSTANTIATED) r = launch_w_if<V, gp::W_128x64>(a, p, st);
+  if (r == NOT_INSTANTIATED) r = launch_w_if<V, gp::W_64x128>(a, p, st);
+  if (r == NOT_INSTANTIATED) r = launch_w_if<V, gp::W_128x128>(a, p, st);
   return r;
 }
 
-template <bool AK, bool BKM, int EPI, bool OUTF32, int CB2>
-int launch_r8_cb(const GemmArgs& a, const R8Plan& pl, hipStream_t st) {
-  Epi e{};
-  e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
-  e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta;
-  R8Args r;
-  r.A = (const bf16*)a.A; r.lda = a.lda; r.B = (const bf16*)a.B; r.ldb = a.ldb;
-  r.M = a.M; r.N = a.N; r.K = a.K; r.n_split = pl.n_split;
-  r.tm = a.M / BIG;
-  r.tn1 = pl.n_split / BIG;
-  r.nb1 = r.tm * r.tn1;
-  r.gm1 = r.tn1 > 0 ? std::max(1, std::min(r.tm, 32 / r.tn1)) : 1;
-  r.tn2 = (a.N - pl.n_split) / (64 * CB2);
-  r.gm2 = std::max(1, std::min(r.tm, 32 / std::max(1, r.tn2)));
-  r.ilv = g_r8_ilv && r.nb1 >= 2 && r.tm * r.tn2 >= 2;
-  const int grid = r.nb1 + r.tm * r.tn2;
-  hipLaunchKernelGGL((gemm8r_kernel<AK, BKM, EPI, OUTF32, CB2>), dim3(grid), dim3(NT2), 0, st, r, e);
-  DTC_CHECK_LAUNCH();
-  note_launch(FAM_R8, BIG, 64 * CB2, 1, CB2, pl.n_split, a.layout, EPI);
-  return 0;
+// Launches what the plan says.  A family's launcher is instantiated for exactly the (layout, epilogue, output)
+// combinations its gp::*_has predicate names (gemm_plan.h, next to the family's plan; the 8-wave configs
+// narrow theirs per config in launch_w_if): the set of kernels in the library is those predicates.
+int launch(const gp::GemmPlan& p, const GemmArgs& a, hipStream_t st) {
+  return with_variant(a.layout, p.epi, p.f32, [&](auto v) {
+    using V = decltype(v);
+    constexpr int L = V::layout, E = V::epi;
+    constexpr bool F = V::f32;
+    switch (p.family) {
+      case gp::FAM_R8: if constexpr (gp::r8_has(L, E, F)) return launch_r8<V>(a, p, st); break;
+      case gp::FAM_N8: if constexpr (gp::n8_has(L, E, F)) return launch_n8<V>(a, p, st); break;
+      case gp::FAM_DMAW: return launch_dmaw<V>(a, p, st);
+      case gp::FAM_BIG: if constexpr (gp::big_has(L, E, F)) return launch_big<V>(a, p, st); break;
+      case gp::FAM_REG:
+      case gp::FAM_DMA64: if constexpr (gp::reg_has(L, E, F)) return launch_reg<V>(a, p, st); break;
+    }
+    return NOT_INSTANTIATED;
+  });
 }
 
-template <int EPI, bool OUTF32, bool BKM = true>
-int launch_r8(const GemmArgs& a, const R8Plan& pl, hipStream_t st) {
-  if (pl.cb2 == 4) return launch_r8_cb<true, BKM, EPI, OUTF32, 4>(a, pl, st);
-  if (pl.cb2 == 2) return launch_r8_cb<true, BKM, EPI, OUTF32, 2>(a, pl, st);
-  return launch_r8_cb<true, BKM, EPI, OUTF32, 1>(a, pl, st);
-}
-
-// ---- gemm8n_kernel plans (layer GEMMs, 128 x 64*CB tiles) ----------------------------------------
-// DTC_GEMM8N bit mask: 1 = forwards and NT dgrads (layout 0), 2 = NN dgrads (layout 1), 4 = also
-// multi-round problems.  A problem takes it when its tile count on 128x192 (CB 3) or 128x256 (CB 4)
-// tiles is exactly one round of 256 (the d_model-wide outputs of GPT-2 small / medium at 8192 tokens:
-// out_proj / fc2 forwards, qkv / fc1 / out_proj dgrads).  Measured (profiles/r3_gemm8n.md): one round
-// wins (fc1 NT dgrad 60.8 -> 44.9 us, fc2 forward 63.5 -> 49.5 us); 3-4 rounds lose to the 128^2 /
-// 256^2 kernels (fc1 forward 75.6 -> 85.6 us: each round pays its own prologue fill and epilogue at
-// one block per CU), and so does a vocab-sized K (the lm_head dgrad keeps its split-K 256^2 kernel).
-static int g_n8_mask = [] { const char* v = getenv("DTC_GEMM8N"); return v ? atoi(v) : 3; }();
-// DTC_N8_CB: only this tile width (3 = 128 x 192, 4 = 128 x 256) for gemm8n plans (0 = 3 then 4; A/B)
-static int g_n8_cb = [] { const char* v = getenv("DTC_N8_CB"); return v ? atoi(v) : 0; }();
-
-// DTC_N8_MINK: smallest K of a one-round gemm8n problem (default 1024; 768 = also the out_proj forward /
-// dgrad, whose plain stores take the overlapped epilogue since the residual add moved to the LayerNorm)
-static int g_n8_mink = [] { const char* v = getenv("DTC_N8_MINK"); return v ? atoi(v) : 1024; }();
-
-static int n8_cb(int layout, int M, int N, int K, int epi) {
-  // K >= 1024: at K = 768 (out_proj forward, 12 K-steps) the one-block-per-CU epilogue (fp32 residual
-  // in + out, nothing to hide it under) costs more than the main loop gains (29.2 vs 26.6 us)
-  if (layout > 1 || !(g_n8_mask & (1 << layout)) || K % 64 || K < 768 || K > 8192 || M < 128) return 0;
-  if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_GELU && epi != EPI_DGELU) return 0;
-  const long tm = (M + 127) / 128;
-  for (int cb : {3, 4}) {
-    if (g_n8_cb && cb != g_n8_cb) continue;
-    const int bn = 64 * cb;
-    if (N % bn) continue;
-    const long t = tm * (N / bn);
-    if ((t == 256 && K >= g_n8_mink) || ((g_n8_mask & 4) && t > 256 && t % 256 == 0)) return cb;
-  }
-  return 0;
-}
-
-template <int CB, bool AK, bool BKM, int EPI, bool OUTF32>
-int launch_n8(const GemmArgs& a, hipStream_t st) {
-  Epi e{};
-  e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
-  e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta;
-  const int tiles_m = (a.M + 127) / 128, tiles_n = a.N / (64 * CB);
-  // an XCD's ~32 concurrent tiles = 8 M-tiles x 4 N-tiles (A panel and B panel both shared)
-  const int gm = tiles_n <= 4 ? std::max(1, std::min(tiles_m, 32 / tiles_n)) : std::min(tiles_m, 8);
-  constexpr int NS = CB == 3 ? 4 : 3;
-  const int grid = std::min(tiles_m * tiles_n, cu_count());  // persistent: one block per CU
-  hipLaunchKernelGGL((gemm8n_kernel<CB, NS, AK, BKM, EPI, OUTF32>), dim3(grid), dim3(NT2), 0, st,
-                     (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m, tiles_n, gm, e);
-  DTC_CHECK_LAUNCH();
-  note_launch(FAM_N8, 128, 64 * CB, 1, CB, 0, a.layout, EPI);
-  return 0;
-}
-
-template <bool AK, bool BKM, int EPI, bool OUTF32>
-int launch_n8cb(const GemmArgs& a, int cb, hipStream_t st) {
-  return cb == 3 ? launch_n8<3, AK, BKM, EPI, OUTF32>(a, st) : launch_n8<4, AK, BKM, EPI, OUTF32>(a, st);
-}
-
-// the (layout, epilogue, output) combinations the layer GEMMs use; -1 = not instantiated
-int launch_n8_any(const GemmArgs& a, int cb, hipStream_t st) {
-  const int epi = a.epi;
-  const bool f32 = a.c_f32 != 0;
-  if (a.layout == 0) {
-    if (epi == EPI_STORE) return f32 ? launch_n8cb<true, true, EPI_STORE, true>(a, cb, st)
-                                     : launch_n8cb<true, true, EPI_STORE, false>(a, cb, st);
-    if (epi == EPI_RESID && f32) return launch_n8cb<true, true, EPI_RESID, true>(a, cb, st);
-    if (epi == EPI_GELU && !f32) return launch_n8cb<true, true, EPI_GELU, false>(a, cb, st);
-    if (epi == EPI_DGELU && !f32) return launch_n8cb<true, true, EPI_DGELU, false>(a, cb, st);
-  } else if (a.layout == 1 && a.N % 8 == 0) {
-    if (epi == EPI_STORE) return f32 ? launch_n8cb<true, false, EPI_STORE, true>(a, cb, st)
-                                     : launch_n8cb<true, false, EPI_STORE, false>(a, cb, st);
-    if (epi == EPI_DGELU && !f32) return launch_n8cb<true, false, EPI_DGELU, false>(a, cb, st);
-  }
-  return -1;
-}
-
+// ---- the pair ----------------------------------------------------------------------------------------------
 // Paired launch: a1 = dgrad (layout 1, whole-K tiles), a2 = weight gradient (layout 2, split-K slabs
 // left for the caller's batched reducer when split > 1).  Only register-staged, BK = 64 plans pair.
 template <class C1, class C2, int BM1, int BM2, bool BKM1 = false>
-int launch_pair_t(const GemmArgs& a1, const Plan& p1, const GemmArgs& a2, const Plan& p2, hipStream_t st) {
+int launch_pair_t(const GemmArgs& a1, const gp::GemmPlan& p1, const GemmArgs& a2, const gp::GemmPlan& p2, hipStream_t st) {
   const GemmLaunch g1 = make_launch<BM1, BM1, true, BKM1>(a1, p1);
   const GemmLaunch g2 = make_launch<BM2, BM2, false, false>(a2, p2);
   if (g1.nblocks % 8 && g2.nblocks % 8) return 1100;  // XCD maps would disagree: not pairable
@@ -3103,12 +2990,12 @@ int launch_pair_t(const GemmArgs& a1, const Plan& p1, const GemmArgs& a2, const 
   hipLaunchKernelGGL((gemm_pair_kernel<C1, C2>), dim3(g1.nblocks + g2.nblocks), dim3(NT), 0, st, g1, g2,
                      second_first);
   DTC_CHECK_LAUNCH();
-  note_launch(FAM_PAIR, BM1, BM2, p2.split, second_first, 0, a1.layout, a1.epi);
+  note_launch(gp::FAM_PAIR, BM1, BM2, p2.split, second_first, 0, a1.layout, a1.epi);
   return 0;
 }
 
 template <int EPI1, bool F1>
-int launch_pair_w(const GemmArgs& a1, const Plan& p1, const GemmArgs& a2, const Plan& p2, hipStream_t st) {
+int launch_pair_w(const GemmArgs& a1, const gp::GemmPlan& p1, const GemmArgs& a2, const gp::GemmPlan& p2, hipStream_t st) {
   using W128 = GemmCfg<128, 128, 64, false, false, EPI_STORE, true>;
   using W64 = GemmCfg<64, 64, 64, false, false, EPI_STORE, true>;
   if (a1.layout == 0) {  // dgrad as NT on the transposed weight (both operands K-major)
@@ -3126,131 +3013,60 @@ int launch_pair_w(const GemmArgs& a1, const Plan& p1, const GemmArgs& a2, const 
                       : launch_pair_t<D, W64, 64, 64>(a1, p1, a2, p2, st);
 }
 
-// ---- 8-wave DMA plans (gemm_dmaw_kernel) for the layer-GEMM shapes ------------------------------
-// Main loop only, L2-hot and back to back (benchmarks/gemm_dma8_micro.hip) the 8-wave configs beat the
-// 4-wave kernels on every layer shape (e.g. fc1 fwd 10.9 -> 8.8 us, fc1 dgrad 26 -> 18 us), but in the
-// step (rocprofv3, profiles/r2_gemm_w8_instep.md) only two keep a gain once their epilogues and
-// in-step operand traffic are counted: the fp32 residual forwards (out_proj, fc2: 128x64 tiles, 16.1
-// -> 14.4 us per call) and the bias-free small weight gradient (out_proj: 64x128, split 8, 11.4 ->
-// 10.8 us).  The 256x128 bf16 forwards tie (14.4 vs 14.7, 22.9 vs 22.6 us: the all-CU epilogue
-// dominates), the dgrads lose (fc1 dgrad 26.5 -> 34-36 us) and unpairing the fc2 / qkv
-// dgrad+weight-gradient launches loses (37.9 -> 49.6, 36.1 -> 43.4 us).  Those configs stay
-// selectable for experiments (DTC_GEMM_W8=2) but are off in the default plan.
-enum { W_NONE = -1, W_256x128 = 0, W_128x64 = 1, W_64x128 = 2, W_128x128 = 3 };
-
-inline int gemm_w8_mode() {  // DTC_GEMM_W8 bits: 1 = measured winners (default), 2 = every config, 4 = 128x64 fp32 dgrads
-  static const int v = [] { const char* s = getenv("DTC_GEMM_W8"); return s ? atoi(s) : 1; }();
-  return v;
+// split-K of the fused lm_head dgrad: the 256^2 plan of the same dgrad (forced 4 / 5 / 8 measured within noise)
+int ce_split(int M, int N, int K) {
+  const gp::GemmPlan p = plan_query(1, M, N, K, EPI_STORE, true, false);
+  return p.family == gp::FAM_BIG ? p.split : 1;
 }
 
-struct WPlan {
-  int cfg, split;
-};
-
-// The 8-wave config (and split-K) of a problem, or W_NONE.  Layer-sized problems only (the lm_head
-// GEMMs keep the 256^2 kernel); weight gradients that fuse their bias column sums (has_colsum) stay
-// on the register-staged kernel, which reads dY through registers.
-WPlan dmaw_plan(int layout, int M, int N, int K, int epi, bool f32, bool has_colsum) {
-  WPlan w{W_NONE, 1};
-  const int mode = gemm_w8_mode();
-  if (!(mode & 7) || K % 64 || M % 8 || N % 8) return w;
-  const bool all = (mode & 2) != 0;
-  auto tiles = [&](int bm, int bn) { return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-  if (layout == 0) {
-    if (all && !f32 && (epi == EPI_STORE || epi == EPI_GELU) && K <= 1024 && tiles(256, 128) >= 128 &&
-        tiles(256, 128) <= 512)
-      w.cfg = W_256x128;
-    else if ((f32 ? (epi == EPI_RESID || epi == EPI_STORE) : epi == EPI_STORE) && K <= 4096 && tiles(128, 64) >= 192 &&
-             tiles(128, 64) <= 512)
-      w.cfg = W_128x64;
-  } else if (layout == 1) {
-    if (all && !f32 && epi == EPI_DGELU && K <= 1024 && tiles(256, 128) >= 128 && tiles(256, 128) <= 512)
-      w.cfg = W_256x128;
-    else if (all && epi == EPI_STORE && K <= 4096 && tiles(64, 128) >= 192 && tiles(64, 128) <= 512)
-      w.cfg = W_64x128;
-    else if ((mode & 4) && epi == EPI_STORE && f32 && K <= 4096 && tiles(128, 64) >= 192 && tiles(128, 64) <= 512)
-      w.cfg = W_128x64;
-  } else if (layout == 2 && epi == EPI_STORE && f32 && !has_colsum && tiles(128, 128) <= 256 &&
-             (all || tiles(128, 128) <= 48)) {
-    // (<= 48 tiles: also GPT-2's [768 x 768] out_proj weight gradient, 53.4 -> 38.3 us)
-    // weight gradient (K = tokens): split-K towards 256 blocks of >= 8 k-steps
-    const int nk = K / 64;
-    const int cfg = tiles(128, 128) >= 32 ? W_128x128 : W_64x128;
-    const long t = cfg == W_128x128 ? tiles(128, 128) : tiles(64, 128);
-    int split = 1;
-    while (t * split * 2 <= 256 && nk / (split * 2) >= 8) split *= 2;
-    w.cfg = cfg;
-    w.split = split;
-  }
-  return w;
-}
-
-template <int BM, int BN, int NS, int WGM, int WGN, bool AK, bool BKM, int EPI, bool OUTF32>
-int launch_w(const GemmArgs& a, int split, hipStream_t st) {
-  Epi e{};
-  e.M = a.M; e.N = a.N; e.C = a.C; e.ldc = a.ldc; e.bias = a.bias; e.aux = a.aux; e.ldaux = a.ldaux;
-  e.aux_out = a.aux_out; e.alpha = a.alpha; e.beta = a.beta; e.labels = a.labels; e.vocab_start = a.vocab_start;
-  e.n_valid = a.n_valid; e.part = a.part; e.label_out = a.label_out; e.part_arg = a.part_arg; e.colsum = nullptr;
-  const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-  e.nparts = tiles_n * WGN;
-  const int ntiles = tiles_m * tiles_n;
-  int gm = wide_gm(tiles_m);
-  if (tiles_n <= 16) gm = std::max(1, std::min(tiles_m, (ntiles / 8 + tiles_n - 1) / tiles_n));
-  const int nk = a.K / 64;
-  const int kps = ((nk + split - 1) / split) * 64;
-  if (split > 1 && a.ws_bytes < (long)split * a.M * a.N * 4) return 1005;
-  hipLaunchKernelGGL((gemm_dmaw_kernel<BM, BN, NS, WGM, WGN, AK, BKM, EPI, OUTF32>), dim3(ntiles * split),
-                     dim3(64 * WGM * WGN), 0, st, (const bf16*)a.A, a.lda, (const bf16*)a.B, a.ldb, a.M, a.N, a.K, tiles_m,
-                     tiles_n, gm, split, kps, (float*)a.workspace, e);
-  DTC_CHECK_LAUNCH();
-  note_launch(FAM_DMAW, BM, BN, split, NS, WGM * 10 + WGN, a.layout, EPI);
-  if (split > 1 && !a.defer_reduce) {
-    long MN = (long)a.M * a.N;
-    hipLaunchKernelGGL(splitk_reduce, dim3((int)((MN / 4 + 255) / 256)), dim3(256), 0, st, (const float*)a.workspace, split,
-                       MN, (float*)a.C, a.ldc, a.N, a.beta);
-    DTC_CHECK_LAUNCH();
-  }
-  return 0;
-}
-
-// only the (config, layout, epilogue) combinations dmaw_plan can return are instantiated
-template <bool AK, bool BKM, int EPI, bool OUTF32>
-int launch_wcfg(const GemmArgs& a, const WPlan& w, hipStream_t st) {
-  if constexpr (!OUTF32 && (EPI == EPI_STORE || EPI == EPI_GELU || EPI == EPI_DGELU) && (AK && (BKM || EPI == EPI_DGELU)))
-    if (w.cfg == W_256x128) return launch_w<256, 128, 2, 4, 2, AK, BKM, EPI, OUTF32>(a, w.split, st);
-  if constexpr (AK && ((OUTF32 && (EPI == EPI_STORE || (BKM && EPI == EPI_RESID))) || (BKM && !OUTF32 && EPI == EPI_STORE)))
-    if (w.cfg == W_128x64) return launch_w<128, 64, 4, 4, 2, AK, BKM, EPI, OUTF32>(a, w.split, st);
-  if constexpr (EPI == EPI_STORE && ((AK && !BKM) || (!AK && !BKM && OUTF32)))
-    if (w.cfg == W_64x128) return launch_w<64, 128, 4, 2, 4, AK, BKM, EPI, OUTF32>(a, w.split, st);
-  if constexpr (!AK && !BKM && OUTF32 && EPI == EPI_STORE)
-    if (w.cfg == W_128x128) return launch_w<128, 128, 4, 4, 2, AK, BKM, EPI, OUTF32>(a, w.split, st);
-  return 1101;  // not instantiated (dmaw_plan and this table disagree)
+inline int set_knob(int& knob, int v) {  // returns the previous value (tests / A/B)
+  const int old = knob;
+  knob = v;
+  return old;
 }
 
 }  // namespace
 
 extern "C" {
 
-// dgrad (a1: layout 1, epi STORE or DGELU) and weight gradient (a2: layout 2, fp32, defer_reduce
-// when split) of one Dense in one launch.  Returns 1100 when the pair cannot share a launch (the
-// caller then issues the two GEMMs separately).
+int dtc_gemm_family_count() { return gp::FAM_COUNT; }
+
+int dtc_gemm(const GemmArgs* a, hipStream_t st) {
+  gp::GemmPlan p;
+  const int rc = validate_and_plan(*a, p);
+  return rc >= 0 ? rc : launch(p, *a, st);
+}
+
+// What dtc_gemm would do with *a, without launching: returns its return code and fills out[8] with the record
+// the launch would write (dtc_gemm_last_launch's fields; zeros when nothing would launch).
+int dtc_gemm_plan(const GemmArgs* a, int out[8]) {
+  gp::GemmPlan p;
+  const int rc = validate_and_plan(*a, p);
+  const int rec[8] = {p.family, p.bm, p.bn, p.split, p.sub, p.aux, a->layout, p.epi};
+  for (int i = 0; i < 8; ++i) out[i] = rc >= 0 ? 0 : rec[i];
+  return rc >= 0 ? rc : 0;
+}
+
+// dgrad (a1: layout 1, or 0 on the transposed weight; epi STORE or DGELU) and weight gradient (a2: layout 2,
+// fp32, defer_reduce when split) of one Dense in one launch.  Returns 1100 when the pair cannot share a launch
+// (the caller then issues the two GEMMs separately): both must plan onto the register-staged kernel, BK = 64,
+// the dgrad unsplit.
 int dtc_gemm_pair(const GemmArgs* a1, const GemmArgs* a2, hipStream_t st) {
   if ((a1->layout != 1 && a1->layout != 0) || a2->layout != 2) return 1100;
   if (a1->K % 64 || a2->K % 64 || a1->N % 8 || a2->M % 8 || a2->N % 8) return 1100;
   if (a1->lda % 8 || a1->ldb % 8 || a1->ldc % 4 || a2->lda % 8 || a2->ldb % 8 || a2->ldc % 4) return 1100;
   if (a1->M <= 0 || a1->N <= 0 || a2->M <= 0 || a2->N <= 0) return 1100;
   if (a2->epi != EPI_STORE || !a2->c_f32 || a2->bias) return 1100;
-  if (big_split(a1->layout, a1->M, a1->N, a1->K) || big_split(2, a2->M, a2->N, a2->K)) return 1100;
-  if (n8_cb(a1->layout, a1->M, a1->N, a1->K, a1->epi)) return 1100;  // dgrad on gemm8n_kernel: own launch
-  if (a1->alpha == 1.f && a1->beta == 0.f && !a1->colsum &&
-      r8_plan(a1->layout, a1->M, a1->N, a1->K, a1->epi, a1->c_f32 != 0).cb2)
-    return 1100;  // dgrad on gemm8r_kernel: own launch (the same plan dtc_gemm picks for it alone)
-  if (dmaw_plan(a1->layout, a1->M, a1->N, a1->K, a1->epi, a1->c_f32 != 0, false).cfg != W_NONE ||
-      dmaw_plan(2, a2->M, a2->N, a2->K, a2->epi, a2->c_f32 != 0, a2->colsum != nullptr).cfg != W_NONE)
-    return 1100;  // the 8-wave kernels run these as two launches
-  const Plan p1 = make_plan(a1->M, a1->N, a1->K, (a1->layout == 1 && a1->epi == EPI_STORE && a1->c_f32) ? 2 : 0);
-  const Plan p2 = make_plan(a2->M, a2->N, a2->K, 1);
-  if (p1.split != 1 || p1.bk != 64 || p2.bk != 64) return 1100;
+  const gp::GemmPlan p1 = plan_of(*a1), p2 = plan_of(*a2);
+  if ((p1.family != gp::FAM_REG && p1.family != gp::FAM_DMA64) || p2.family != gp::FAM_REG) return 1100;  // own launches
+  // Kept from before the plan: three shape tests that also refuse dgrads dtc_gemm runs register-staged (a
+  // 256^2 shape at K >= 16384 that is not an fp32 store; a gemm8n shape with alpha / beta or a column sum; a
+  // gemm8r shape whose (layout, output) gemm8r does not instantiate).
+  if (gp::big_split(a1->layout, a1->M, a1->N, a1->K, g_knobs) || gp::n8_cb(a1->layout, a1->M, a1->N, a1->K, a1->epi, g_knobs) ||
+      (a1->alpha == 1.f && a1->beta == 0.f && !a1->colsum &&
+       gp::r8_plan(a1->layout, a1->M, a1->N, a1->K, a1->epi, a1->c_f32 != 0, cu_count(), g_knobs).cb2))
+    return 1100;
+  if (p1.err || p1.split != 1 || p1.bk != 64 || p2.bk != 64) return 1100;
   if (p2.split > 1 && (!a2->defer_reduce || a2->ws_bytes < (long)p2.split * a2->M * a2->N * 4)) return 1100;
   if (a1->epi == EPI_DGELU && !a1->c_f32) return launch_pair_w<EPI_DGELU, false>(*a1, p1, *a2, p2, st);
   if (a1->epi == EPI_STORE && a1->c_f32) return launch_pair_w<EPI_STORE, true>(*a1, p1, *a2, p2, st);
@@ -3260,9 +3076,6 @@ int dtc_gemm_pair(const GemmArgs* a1, const GemmArgs* a2, hipStream_t st) {
 
 // Fused lm_head backward (ce_dgrad256_kernel): dX [M][N] fp32 (= sum of the split-K slabs, written
 // by splitk_reduce), dlogits [M][K] bf16, colpart [2*ceil(M/256)][K] fp32.  K % 64 == 0, N % 8 == 0.
-// split-K of the fused lm_head dgrad: the big_split plan (forced 4 / 5 / 8 measured within noise)
-static int ce_split(int M, int N, int K) { return std::max(1, big_split(1, M, N, K)); }
-
 long dtc_ce_dgrad_workspace_bytes(int M, int N, int K) {
   const int split = ce_split(M, N, K);
   return split > 1 ? (long)split * M * N * 4 : (long)M * N * 4;
@@ -3282,13 +3095,13 @@ int dtc_ce_dgrad(const bf16* logits, long ldl, const float* lse, const int* labe
   a.tiles_m = (M + BIG - 1) / BIG;
   a.tiles_n = (N + BIG - 1) / BIG;
   const int ntiles = a.tiles_m * a.tiles_n;
-  a.gm = a.tiles_m;
+  a.gm = a.tiles_m;  // its own form: an XCD's share of the blocks (tiles x split), never DTC_WIDE_GM
   if (a.tiles_n <= 16) a.gm = std::max(1, std::min(a.tiles_m, (ntiles * split / 8 + a.tiles_n - 1) / a.tiles_n));
   a.split = split;
   a.kps = big_kps(K, split);
   hipLaunchKernelGGL(ce_dgrad256_kernel, dim3(ntiles * split), dim3(NT2), 0, st, a);
   DTC_CHECK_LAUNCH();
-  note_launch(FAM_CE_DGRAD, BIG, BIG, split, 0, 0, 1, EPI_STORE);
+  note_launch(gp::FAM_CE_DGRAD, BIG, BIG, split, 0, 0, 1, EPI_STORE);
   const long MN = (long)M * N;
   hipLaunchKernelGGL(splitk_reduce, dim3((int)((MN / 4 + 255) / 256)), dim3(256), 0, st, (const float*)ws, split, MN,
                      dx, (long)N, N, 0.f);
@@ -3318,72 +3131,53 @@ int dtc_gemm_ln(const LnArgs* a, hipStream_t st) {
                        (const bf16*)a->A, a->lda, (const bf16*)a->B, a->ldb, a->M, a->N, a->K, tiles_m, tiles_n, tiles_m,
                        1, a->K, nullptr, e);
   DTC_CHECK_LAUNCH();
-  note_launch(FAM_LN, 128, 64, 1, a->bwd ? 1 : 0, 0, 0, a->bwd ? EPI_LN_BWD : EPI_RESID_LN);
+  note_launch(gp::FAM_LN, 128, 64, 1, a->bwd ? 1 : 0, 0, 0, a->bwd ? EPI_LN_BWD : EPI_RESID_LN);
   return 0;
 }
 
 long dtc_gemm_ln_sync_words(int M, int N) { return (long)M * (N / 32) + (long)(M / 128) * (N / 64); }
 
-int dtc_lmhead_nparts(int M, int N, int K) { return big_split(0, M, N, K) ? ((N + 255) / 256) * 4 : ((N + 127) / 128) * 2; }
+// ---- planning queries: what dtc_gemm will do, read off the same plan ------------------------------------------
+// row-statistics parts per row of the lm_head forward [M x N x K]: 4 per 256-wide tile, 2 per 128-wide one
+int dtc_lmhead_nparts(int M, int N, int K) {
+  const gp::GemmPlan p = plan_query(0, M, N, K, EPI_LMHEAD, false, false);
+  // Kept from before the plan: at K >= 16384 with at most 256 tiles of 256^2 (a split-K shape) the head runs on
+  // 128^2 tiles, yet this has always answered with the 256^2 count.
+  if (p.bn == BIG || gp::big_split(0, M, N, K, g_knobs)) return ((N + 255) / 256) * 4;
+  return ((N + 127) / 128) * 2;
+}
 
 // split-K factor dtc_gemm will use for a weight-gradient (layout 2) problem (1 = none); has_db: the
-// caller wants the bias gradient fused (GemmArgs.colsum), which pins the register-staged kernel
+// caller wants the bias gradient fused (GemmArgs.colsum), which keeps it off the 8-wave kernel
 int dtc_gemm_wgrad_split(int M, int N, int K, int has_db) {
-  if (const int bs = big_split(2, M, N, K)) return bs;
-  if (!has_db) {
-    const WPlan w = dmaw_plan(2, M, N, K, EPI_STORE, true, false);
-    if (w.cfg != W_NONE) return w.split;
-  }
-  return make_plan(M, N, K, 1).split;
+  return plan_query(2, M, N, K, EPI_STORE, true, has_db != 0).split;
 }
 
-// 1 if the weight-gradient GEMM runs on the register-staged kernel, which can fuse the bias
-// gradient (GemmArgs.colsum); the 256^2 and DMA kernels cannot
+// 1 if the weight-gradient GEMM can fuse the bias gradient (GemmArgs.colsum): the register-staged kernel
+// always, gemm8p_kernel unless DTC_WGRAD_CS256=0 (dtc_gemm then refuses the column sum with 1009)
 int dtc_gemm_wgrad_fuses_colsum(int M, int N, int K) {
-  if (big_split(2, M, N, K)) return g_wgrad_cs256 ? 1 : 0;  // gemm8p_kernel sums it with MFMAs
-  return 1;  // the register-staged 64^2 / 128^2 weight-gradient plans (never the DMA variant)
+  return plan_query(2, M, N, K, EPI_STORE, true, true).err != 1009;
 }
 
+// Split-K workspace for any fp32-store problem of this layout and size.  Kept from before the plan, as an
+// upper bound over the splitting families instead of the one plan: it is asked without the epilogue and output
+// type, and it has always reserved slabs for some problems that then run unsplit (NT 4096 x 1536 x 16384 with a
+// bf16 output; an NN shape gemm8n takes at K = 8192), and none for a few ragged K >= 16384 NN shapes.
 long dtc_gemm_workspace_bytes(int layout, int M, int N, int K) {
-  Plan p = make_plan(M, N, K, layout == 2 ? 1 : (layout == 1 ? 2 : 0));
-  const int bs = big_split(layout, M, N, K);
-  int split = bs ? bs : p.split;
-  if (layout == 2 && !bs) split = std::max(split, dmaw_plan(2, M, N, K, EPI_STORE, true, false).split);
+  const int bs = gp::big_split(layout, M, N, K, g_knobs);
+  int split = bs ? bs : gp::reg_plan(M, N, K, layout == 2 ? 1 : (layout == 1 ? 2 : 0), g_knobs).split;
+  if (layout == 2 && !bs) split = std::max(split, gp::dmaw_plan(2, M, N, K, EPI_STORE, true, false, g_knobs).split);
   return split > 1 ? (long)split * M * N * 4 : 0;
 }
 
-// weight gradients split-K on the 256^2 kernel (DTC_WGRAD256 at load time); returns the previous value
-int dtc_gemm_set_wgrad256(int on) {
-  const int old = g_wgrad256;
-  g_wgrad256 = on;
-  return old;
-}
-
-// gemm8n layout mask (DTC_GEMM8N at load time); returns the previous mask (tests / A/B)
-int dtc_gemm_set_n8(int mask) {
-  const int old = g_n8_mask;
-  g_n8_mask = mask;
-  return old;
-}
-
-// 256 x 192 split-K plan of launch_big (DTC_BIG_CB3 at load time); returns the previous value
-int dtc_gemm_set_big_cb3(int on) {
-  const int old = g_big_cb3;
-  g_big_cb3 = on;
-  return old;
-}
-
-int dtc_gemm_set_n8_mink(int k) {
-  const int old = g_n8_mink;
-  g_n8_mink = k;
-  return old;
-}
-
-int dtc_gemm_set_n8_cb(int cb) {
-  const int old = g_n8_cb;
-  g_n8_cb = cb;
-  return old;
-}
+// ---- knobs at run time (tests / A/B): each returns the previous value ------------------------------------------
+int dtc_gemm_set_wgrad256(int on) { return set_knob(g_knobs.wgrad256, on); }    // DTC_WGRAD256
+int dtc_gemm_set_n8(int mask) { return set_knob(g_knobs.n8_mask, mask); }       // DTC_GEMM8N
+int dtc_gemm_set_big_cb3(int on) { return set_knob(g_knobs.big_cb3, on); }      // DTC_BIG_CB3
+int dtc_gemm_set_n8_mink(int k) { return set_knob(g_knobs.n8_mink, k); }        // DTC_N8_MINK
+int dtc_gemm_set_n8_cb(int cb) { return set_knob(g_knobs.n8_cb, cb); }          // DTC_N8_CB
+int dtc_gemm_set_r8(int mask) { return set_knob(g_knobs.r8_mask, mask); }       // DTC_GEMM8R
+int dtc_gemm_set_r8_ilv(int on) { return set_knob(g_knobs.r8_ilv, on); }        // DTC_R8_ILV
 
 int dtc_wg_entry_bytes() { return (int)sizeof(WgEntry); }
 int dtc_wg_max() { return WG_MAX; }
@@ -3407,8 +3201,7 @@ int dtc_wgrad_group(const WgBatch* in, hipStream_t st) {
     // larger operand dY is read once and the smaller X panels are the re-read ones: used when M >= 2N
     // (the lm_head: -60 us/step, profiles/r5_wg_nfast_ab.log; also qkv / fc1: a further -15 us,
     // r5_wg_nfast2_ab.log).  DTC_WG_NFAST=0 keeps M-fastest everywhere.
-    static const bool nfast_on = [] { const char* v = getenv("DTC_WG_NFAST"); return !v || atoi(v) != 0; }();
-    w.nfast = nfast_on && w.M >= 2 * w.N;
+    w.nfast = g_knobs.wg_nfast && w.M >= 2 * w.N;
   }
   b.ntiles = t;
   // tail split: the last (t mod CUs) tiles as K-pieces when every one of them belongs to a problem without
@@ -3432,25 +3225,12 @@ int dtc_wgrad_group(const WgBatch* in, hipStream_t st) {
   if (!tail) b.tail_slab = nullptr;
   hipLaunchKernelGGL(gemm8p_group_kernel, dim3(t - tail + tail * b.tail_split), dim3(NT2), 0, st, b);
   DTC_CHECK_LAUNCH();
-  note_launch(FAM_WGROUP, BIG, BIG, b.tail_split, tail, t, 2, EPI_STORE);
+  note_launch(gp::FAM_WGROUP, BIG, BIG, b.tail_split, tail, t, 2, EPI_STORE);
   if (tail) {
     hipLaunchKernelGGL(wg_tail_reduce, dim3(tail * 8), dim3(WGT_THREADS), 0, st, b);
     DTC_CHECK_LAUNCH();
   }
   return 0;
-}
-
-// gemm8r plan mask (DTC_GEMM8R at load time); returns the previous value (tests / A/B)
-int dtc_gemm_set_r8(int mask) {
-  const int old = g_r8_mask;
-  g_r8_mask = mask;
-  return old;
-}
-
-int dtc_gemm_set_r8_ilv(int on) {
-  const int old = g_r8_ilv;
-  g_r8_ilv = on;
-  return old;
 }
 
 // the record of the last launch (LastLaunch): out[8] = family, BM, BN, split-K, sub-variant, aux, layout, epilogue
@@ -3459,111 +3239,6 @@ int dtc_gemm_last_launch(int* out) {
   out[0] = l.family; out[1] = l.bm; out[2] = l.bn; out[3] = l.split;
   out[4] = l.sub; out[5] = l.aux; out[6] = l.layout; out[7] = l.epi;
   return 0;
-}
-
-int dtc_gemm(const GemmArgs* a, hipStream_t st) {
-  if (a->K % 32 != 0) return 1001;               // K must be a multiple of 32 (BK = 64, or 32)
-  if (a->lda % 8 || a->ldb % 8 || a->ldc % 4) return 1002;  // 16-B row alignment
-  if (a->M <= 0 || a->N <= 0) return 0;
-  // the evaluation head plans as the training head (same kernel family, tile and part count); only the
-  // two dispatch sites that carry EPI_LMHEAD tell them apart
-  const bool eval = a->epi == EPI_LMHEAD_EVAL;
-  const int epi = eval ? EPI_LMHEAD : a->epi;
-  const bool f32 = a->c_f32 != 0;
-  if (eval && (a->layout != 0 || f32 || !a->part_arg || !a->part || !a->label_out || !a->labels)) return 1011;
-  if (a->layout <= 1 && !a->colsum && a->alpha == 1.f && a->beta == 0.f &&
-      !n8_cb(a->layout, a->M, a->N, a->K, epi)) {
-    const R8Plan pl = r8_plan(a->layout, a->M, a->N, a->K, epi, f32);
-    if (pl.cb2 && a->layout == 0) {
-      if (epi == EPI_STORE) return f32 ? launch_r8<EPI_STORE, true>(*a, pl, st) : launch_r8<EPI_STORE, false>(*a, pl, st);
-      if (epi == EPI_GELU) return launch_r8<EPI_GELU, false>(*a, pl, st);
-      if (epi == EPI_DGELU) return launch_r8<EPI_DGELU, false>(*a, pl, st);
-    } else if (pl.cb2 && !f32) {  // NN (W MN-major): the fc2 dgrad + dGELU, bf16 dgrads
-      if (epi == EPI_DGELU) return launch_r8<EPI_DGELU, false, false>(*a, pl, st);
-      if (epi == EPI_STORE) return launch_r8<EPI_STORE, false, false>(*a, pl, st);
-    }
-  }
-  if (a->layout <= 1 && !a->colsum && a->alpha == 1.f && a->beta == 0.f) {
-    const int cb = n8_cb(a->layout, a->M, a->N, a->K, epi);
-    if (cb) {
-      const int r = launch_n8_any(*a, cb, st);
-      if (r >= 0) return r;
-    }
-  }
-  if (a->layout <= 2 && !(a->layout == 2 && (a->bias || big_split(2, a->M, a->N, a->K)))) {
-    const WPlan w = dmaw_plan(a->layout, a->M, a->N, a->K, epi, f32, a->colsum != nullptr);
-    if (w.cfg != W_NONE) {
-      if (a->layout == 0) {
-        if (epi == EPI_STORE) return f32 ? launch_wcfg<true, true, EPI_STORE, true>(*a, w, st)
-                                         : launch_wcfg<true, true, EPI_STORE, false>(*a, w, st);
-        if (epi == EPI_GELU && !f32) return launch_wcfg<true, true, EPI_GELU, false>(*a, w, st);
-        if (epi == EPI_RESID && f32) return launch_wcfg<true, true, EPI_RESID, true>(*a, w, st);
-      } else if (a->layout == 1) {
-        if (epi == EPI_DGELU && !f32) return launch_wcfg<true, false, EPI_DGELU, false>(*a, w, st);
-        if (epi == EPI_STORE) return f32 ? launch_wcfg<true, false, EPI_STORE, true>(*a, w, st)
-                                         : launch_wcfg<true, false, EPI_STORE, false>(*a, w, st);
-      } else if (epi == EPI_STORE && f32) {
-        return launch_wcfg<false, false, EPI_STORE, true>(*a, w, st);
-      }
-    }
-  }
-  if (a->layout == 0) {
-    Plan p = make_plan(a->M, a->N, a->K, 0);
-    const int bs0 = big_split(0, a->M, a->N, a->K);
-    // the split-K slabs hold bare accumulators and splitk_reduce knows no bias: refuse it, do not drop it
-    if (bs0 > 1 && epi == EPI_STORE && f32 && a->bias) return 1010;
-    if (bs0 > 1 && epi == EPI_STORE && f32) return launch_big<true, true, EPI_STORE, true>(*a, bs0, st);
-    if (bs0 == 1) {
-      if (epi == EPI_LMHEAD)
-        return eval ? launch_big<true, true, EPI_LMHEAD_EVAL, false>(*a, 1, st)
-                    : launch_big<true, true, EPI_LMHEAD, false>(*a, 1, st);
-      if (epi == EPI_GELU) return launch_big<true, true, EPI_GELU, false>(*a, 1, st);
-      if (epi == EPI_DGELU && !f32) return launch_big<true, true, EPI_DGELU, false>(*a, 1, st);
-      if (epi == EPI_RESID) return launch_big<true, true, EPI_RESID, true>(*a, 1, st);
-      if (epi == EPI_STORE)
-        return f32 ? launch_big<true, true, EPI_STORE, true>(*a, 1, st) : launch_big<true, true, EPI_STORE, false>(*a, 1, st);
-      return 1003;
-    }
-    if (epi == EPI_LMHEAD) {
-      if (p.bk != 64) return 1008;
-      p.bm = p.bn = 128;
-      return eval ? launch_t<128, 128, true, true, EPI_LMHEAD_EVAL, false>(*a, p, st)
-                  : launch_t<128, 128, true, true, EPI_LMHEAD, false>(*a, p, st); }
-    if (epi == EPI_GELU) return launch_sz<true, true, EPI_GELU, false>(*a, p, st);
-    if (epi == EPI_DGELU && !f32) return launch_sz<true, true, EPI_DGELU, false>(*a, p, st);  // NT dgrad (W^T)
-    if (epi == EPI_RESID) return launch_sz<true, true, EPI_RESID, true>(*a, p, st);
-    if (epi == EPI_STORE) return f32 ? launch_sz<true, true, EPI_STORE, true>(*a, p, st)
-                                     : launch_sz<true, true, EPI_STORE, false>(*a, p, st);
-    return 1003;
-  }
-  if (a->layout == 1) {
-    if (a->N % 8) return 1004;
-    {
-      const int bs = big_split(1, a->M, a->N, a->K);
-      if (bs > 1 && epi == EPI_STORE && f32) return launch_big<true, false, EPI_STORE, true>(*a, bs, st);
-      if (bs == 1 && a->K < 16384) {
-        if (epi == EPI_DGELU) return launch_big<true, false, EPI_DGELU, false>(*a, 1, st);
-        if (epi == EPI_STORE)
-          return f32 ? launch_big<true, false, EPI_STORE, true>(*a, 1, st) : launch_big<true, false, EPI_STORE, false>(*a, 1, st);
-      }
-    }
-    Plan p = make_plan(a->M, a->N, a->K, (epi == EPI_STORE && f32) ? 2 : 0);
-    if (p.split > 1 && a->ws_bytes < (long)p.split * a->M * a->N * 4) return 1005;
-    if (epi == EPI_DGELU) return launch_sz<true, false, EPI_DGELU, false>(*a, p, st);
-    if (epi == EPI_STORE) return f32 ? launch_sz<true, false, EPI_STORE, true>(*a, p, st)
-                                     : launch_sz<true, false, EPI_STORE, false>(*a, p, st);
-    return 1003;
-  }
-  if (a->layout == 2) {
-    if (a->M % 8 || a->N % 8) return 1004;
-    if (epi != EPI_STORE || !f32 || a->bias) return 1003;
-    if (a->colsum && !dtc_gemm_wgrad_fuses_colsum(a->M, a->N, a->K)) return 1009;
-    if (const int bs = big_split(2, a->M, a->N, a->K)) return launch_big<false, false, EPI_STORE, true>(*a, bs, st);
-    Plan p = make_plan(a->M, a->N, a->K, 1);
-    if (p.split > 1 && a->ws_bytes < (long)p.split * a->M * a->N * 4) return 1005;
-    return launch_sz<false, false, EPI_STORE, true>(*a, p, st);
-  }
-  return 1006;
 }
 
 }  // extern "C"

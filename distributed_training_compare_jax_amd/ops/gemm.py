@@ -122,9 +122,10 @@ def _gemm_args(layout: int, M: int, N_: int, K: int, a, lda: int, b, ldb: int, c
     return args
 
 
-# kernel families of csrc/gemm.hip (enum FAM_* there, keep in sync)
+# kernel families of csrc/gemm_plan.h (enum FAM_* there; last_launch checks the count once)
 FAMILIES = ("none", "gemm_kernel", "gemm_dma_kernel", "gemm_dmaw_kernel", "gemm8p_kernel", "gemm8r_kernel",
             "gemm8n_kernel", "gemm_pair_kernel", "gemm8p_group_kernel", "ce_dgrad256_kernel", "gemm_dmaw_kernel_ln")
+_FAMILIES_CHECKED = [False]
 
 LastLaunch = collections.namedtuple("LastLaunch", "family bm bn split_k sub aux layout epi")
 
@@ -137,6 +138,9 @@ def last_launch() -> LastLaunch:
     CB2 for ``gemm8r_kernel`` (``aux`` = columns on 256^2 tiles); ``gemm_pair_kernel``: ``bm`` / ``bn`` are the
     dgrad / weight-gradient tiles and ``split_k`` the weight gradient's; ``gemm8p_group_kernel``: ``split_k`` =
     tail split, ``sub`` = tail tiles, ``aux`` = all tiles.  Tests assert it; nothing on the hot path reads it."""
+    if not _FAMILIES_CHECKED[0]:
+        assert N.lib().dtc_gemm_family_count() == len(FAMILIES)
+        _FAMILIES_CHECKED[0] = True
     out = (ctypes.c_int * 8)()
     N.check(N.lib().dtc_gemm_last_launch(out), "dtc_gemm_last_launch")
     v = list(out)
