@@ -236,8 +236,24 @@ class GPTStage:
                 sq = self.wg_sq
             G.wgrad_group(q, beta, red=self.red, sq=sq)
 
-    def use_wgrad_sumsq(self, sq: torch.Tensor):
-        """From now on the grouped launch writes its tiles' Σ dW² into ``sq`` (FusedAdamW.set_fused_sumsq)."""
+    def wgrad_problems(self):
+        """The problems ``(dw, n_out, n_in)`` of the stage's ONE grouped weight-gradient launch (``wg_group`` 0), in
+        launch order, from the layout alone: the lm_head's (unless the vocab-chunked head runs it apart), then per
+        layer in backward order fc2, fc1, out_proj, qkv.  What the first flush records as ``wg_seen``; a resumed
+        process registers the grad-norm partials from this list before its first step."""
+        f = self.flat
+        names = []
+        if self.layout.has_head and not (_CE_CHUNK > 0 and self.v_local > _CE_CHUNK):
+            names.append("lm_head.w")
+        for l in reversed(list(self.layout.layers)):
+            names += [f"h.{l}.{n}.w" for n in ("fc2", "fc1", "out", "qkv")]
+        return [(dw, dw.shape[0], dw.shape[1]) for dw in (f.g(n) for n in names)]
+
+    def use_wgrad_sumsq(self, sq: torch.Tensor, problems=None):
+        """From now on the grouped launch writes its tiles' Σ dW² into ``sq`` (FusedAdamW.set_fused_sumsq);
+        ``problems``: the launch's problems when no flush has recorded them yet (:meth:`wgrad_problems`)."""
+        if problems is not None:
+            self.wg_seen = list(problems)
         self.wg_sq = sq
         self._wg_keys = sorted(dw.data_ptr() for dw, _, _ in self.wg_seen)
 

@@ -1014,25 +1014,43 @@ class Engine:
         self.steps_done += 1
         st = self.stage
         if st.wg_record and st.wg_sq is None and st.wg_seen is not None:  # after the first (eager) step
-            ranges, tiles = [], 0
-            base = self.flat.grads.data_ptr()
-            for dw, m, n in st.wg_seen:
-                ranges.append(((dw.data_ptr() - base) // 4, dw.numel()))
-                tiles += G.wgrad_tiles(m, n)
-            nwg = tiles * G.WG_SQ_SLOTS
-            # the embedding tables' Σg² from the embedding backward itself (its last kernel writes the final
-            # rows): no 154 MB norm pass over a table whose untouched rows are zero (GPT-2 small: -25 us/step)
-            emb = 0
-            if self._emb_fused_norm():
-                for name in ("wte", "wpe"):
-                    g = self.flat.g(name)
-                    ranges.append(((g.data_ptr() - base) // 4, g.numel()))
-                emb = E.embed_sq_slots(self.b_local, self.T, self._D)
-            part = self.opt.set_fused_sumsq(ranges, nwg + emb)
-            st.use_wgrad_sumsq(part[:nwg])
-            if emb:
-                st.emb_sq = part[nwg:]
+            self.register_fused_norm(st.wg_seen)
         return self.loss
+
+    def register_fused_norm(self, problems):
+        """Switch the global norm to the fused Σg² partials: the grouped weight-gradient launch's per-tile Σ dW² over
+        ``problems`` (``(dw, n_out, n_in)`` in launch order) and, where it applies, the embedding backward's own.
+        :meth:`run_step` calls it with the problems the first, eager step recorded; :meth:`resume_fused_norm` with
+        the stage's own list.  ``GPTStage.flush_wgrads`` then refuses a launch over other problems."""
+        st = self.stage
+        ranges, tiles = [], 0
+        base = self.flat.grads.data_ptr()
+        for dw, m, n in problems:
+            ranges.append(((dw.data_ptr() - base) // 4, dw.numel()))
+            tiles += G.wgrad_tiles(m, n)
+        nwg = tiles * G.WG_SQ_SLOTS
+        # the embedding tables' Σg² from the embedding backward itself (its last kernel writes the final
+        # rows): no 154 MB norm pass over a table whose untouched rows are zero (GPT-2 small: -25 us/step)
+        emb = 0
+        if self._emb_fused_norm():
+            for name in ("wte", "wpe"):
+                g = self.flat.g(name)
+                ranges.append(((g.data_ptr() - base) // 4, g.numel()))
+            emb = E.embed_sq_slots(self.b_local, self.T, self._D)
+        part = self.opt.set_fused_sumsq(ranges, nwg + emb)
+        st.use_wgrad_sumsq(part[:nwg], problems)
+        if emb:
+            st.emb_sq = part[nwg:]
+
+    def resume_fused_norm(self):
+        """After a checkpoint was loaded into an engine that has not stepped yet: register the fused Σg² partials now
+        instead of after the first step.  The first step of a resumed process is a later step of the run it
+        continues, where the norm comes from the partials (another summation order than the plain pass: a last-bit
+        difference in the clip factor flips bf16 mirror roundings); with this it computes what that step computes
+        in the uninterrupted run.  A freshly started run is untouched."""
+        st = self.stage
+        if st.wg_record and st.wg_sq is None and self.steps_done == 0:
+            self.register_fused_norm(st.wgrad_problems())
 
     # ------------------------------------------------------------------ evaluation
     def _eval_fn(self):

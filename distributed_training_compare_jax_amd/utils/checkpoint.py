@@ -9,6 +9,12 @@ DP/TP/PP layout (vocab rows trimmed to the canonical ``vocab_size``, whatever TP
 them), so a run can be converted between strategies.  Resume compares the map with this rank's
 flat-buffer slots before touching any buffer, and every rank fails together when one rank's check
 fails.  Files are loaded with ``weights_only=True``.
+
+Contract (``tests/test_resume_gpu.py``): a resumed run equals the uninterrupted one bit for bit on every single-GPU
+mode and on tp2 / pp2 / dp2.  Not part of a checkpoint and rebuilt by :func:`load_into`: the bf16 mirror, its
+transposed twin, the e4m3 / MXFP8 weight mirrors (``FlatParams.refresh_mirror``) and the registration of the fused
+Σg² partials (``Engine.resume_fused_norm``: the first step of a resumed process is a later step of the run, whose
+global norm is summed from those partials); the dropout stream and the learning rate are functions of ``step_t``.
 """
 
 from __future__ import annotations
@@ -196,6 +202,8 @@ def load_into(eng, output_dir: str, step: int):
     eng.opt.step_t.copy_(st["step_t"].to(f.device))
     # (under ZeRO-1 every rank's params file holds the full, gathered parameters)
     f.refresh_mirror()
+    if hasattr(eng, "resume_fused_norm"):
+        eng.resume_fused_norm()  # the next step is a later step of the run: its norm comes from the fused partials
     return int(st["step"])
 
 
