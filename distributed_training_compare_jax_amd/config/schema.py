@@ -55,10 +55,20 @@ are optional and default to the reference behaviour:
   local rows run as k microbatches of ``b_local / k`` rows inside one step (one update, one loss, one CSV row), the
   gradients accumulated in place, so the peak activation memory is that of one microbatch.  Every DP / TP / ZeRO-1
   layout and transport (``train/engine.py``); pp > 1 accumulates through ``pp_microbatches`` instead.
-* ``OptimConfig.lr_schedule`` (``constant`` | ``warmup_cosine``) with ``lr_warmup_steps`` (W), ``lr_decay_steps``
+* ``OptimConfig.lr_schedule`` (``constant`` | ``warmup_cosine`` | ``warmup_linear`` | ``wsd``) with ``lr_warmup_steps`` (W), ``lr_decay_steps``
   (N, warmup included) and ``lr_min_ratio`` (r): ``optax.warmup_cosine_decay_schedule(0, lr, W, N, lr * r)`` under
   ``scale_by_schedule``, evaluated on the device once per step from the step counter (``csrc/elementwise.hip``), so
   a captured step replays the schedule instead of one frozen rate; :meth:`OptimConfig.lr_at` is its float64 value.
+  ``wsd`` (warmup, stable, decay) adds ``lr_cooldown_steps`` (C >= 1, W + C <= N): ``lr * c / W`` for c < W, ``lr``
+  up to update N - C, ``lr * (1 - (1 - r) (c - (N - C)) / C)`` over the last C, ``lr * r`` from update N on (c = t - 1);
+  ``warmup_linear`` is wsd with C = N - W, evaluated by the same arithmetic (the name ``linear`` is not accepted).
+* ``OptimConfig.param_groups``: a list of ``{match: [fnmatch patterns on ParamSpec.name], weight_decay: x, lr_scale:
+  s}`` (either value optional, not both missing), normalised to a tuple of frozen :class:`ParamGroup` records.  The
+  first group that matches a parameter gives it its decay (in place of the global one) and multiplies its scheduled
+  rate by ``lr_scale``; unmatched parameters keep the global decay and scale 1.  Unknown keys, an empty ``match``,
+  negative or non-finite values raise ``ValueError``; the engine also refuses a pattern that matches no parameter
+  of the model.  The groups live inside the fused AdamW kernels (``ops/optim.py GroupTable``); a checkpoint records
+  :meth:`OptimConfig.groups_key` ('' without groups).
 * ``TrainConfig.eval_every`` (default 0 = off) / ``eval_batches`` (default 8): every ``eval_every`` optimizer updates and
   after the last one, a forward-only pass over ``eval_batches`` held-out batches of ``batch`` rows (the synthetic
   stream read from ``data/synthetic.py EVAL_POS_BASE`` on: the same tokens at every evaluation and under every
@@ -73,7 +83,7 @@ from __future__ import annotations
 
 import dataclasses
 from dataclasses import dataclass, field, replace
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Optional, Tuple
 
 PyTree = Any
 
@@ -122,6 +132,52 @@ class ModelConfig:
         return 6.0 * mm + 3.0 * 2.0 * attn
 
 
+_SCHEDULES = ("constant", "warmup_cosine", "warmup_linear", "wsd")
+
+
+@dataclass(frozen=True)
+class ParamGroup:
+    """One entry of ``OptimConfig.param_groups``: the parameters whose name matches any ``match`` pattern (fnmatch on
+    ``ParamSpec.name``) take ``weight_decay`` in place of the global one and ``lr_scale`` times the (scheduled)
+    rate; None = the default (the global decay, scale 1)."""
+    match: Tuple[str, ...]
+    weight_decay: Optional[float] = None
+    lr_scale: Optional[float] = None
+
+    def matches(self, name: str) -> bool:
+        import fnmatch
+
+        return any(fnmatch.fnmatchcase(name, pat) for pat in self.match)
+
+
+def _param_group(i: int, g) -> ParamGroup:
+    import math
+
+    if isinstance(g, ParamGroup):
+        g = dict(match=g.match, weight_decay=g.weight_decay, lr_scale=g.lr_scale)
+    if not isinstance(g, dict):
+        raise ValueError(f"param_groups[{i}]={g!r}: expected a mapping with 'match' and 'weight_decay' / 'lr_scale'")
+    unknown = sorted(set(g) - {"match", "weight_decay", "lr_scale"})
+    if unknown:
+        raise ValueError(f"param_groups[{i}]: unknown key {unknown[0]!r} (expected match, weight_decay, lr_scale)")
+    match = g.get("match")
+    if isinstance(match, str):
+        match = [match]
+    if not match or not all(isinstance(m, str) and m for m in match):
+        raise ValueError(f"param_groups[{i}]: match={g.get('match')!r}: expected a non-empty list of name patterns")
+    vals = {}
+    for k in ("weight_decay", "lr_scale"):
+        v = g.get(k)
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"param_groups[{i}]: {k}={v!r}: expected a finite number >= 0")
+            v = float(v)
+        vals[k] = v
+    if vals["weight_decay"] is None and vals["lr_scale"] is None:
+        raise ValueError(f"param_groups[{i}] (match={list(match)!r}) sets neither weight_decay nor lr_scale")
+    return ParamGroup(tuple(match), vals["weight_decay"], vals["lr_scale"])
+
+
 @dataclass(frozen=True)
 class OptimConfig:
     lr: float
@@ -132,31 +188,54 @@ class OptimConfig:
     b2: float = 0.999
     eps: float = 1e-8
     # --- extensions (defaults = reference behaviour: one constant rate) ---
-    lr_schedule: str = "constant"  # constant | warmup_cosine
+    lr_schedule: str = "constant"  # constant | warmup_cosine | warmup_linear | wsd
     lr_warmup_steps: int = 0       # W: linear warmup from 0 over the first W updates
-    lr_decay_steps: int = 0        # N: the cosine reaches lr * lr_min_ratio at update N (warmup included)
+    lr_decay_steps: int = 0        # N: the decay reaches lr * lr_min_ratio at update N (warmup included)
     lr_min_ratio: float = 0.0      # r: the floor as a fraction of lr
+    lr_cooldown_steps: int = 0     # C (wsd): the linear decay covers the last C of the N updates
+    # parameter groups: [{match: [patterns], weight_decay: .., lr_scale: ..}], first match wins (ParamGroup)
+    param_groups: Tuple[ParamGroup, ...] = ()
 
     def __post_init__(self):
-        if self.lr_schedule not in ("constant", "warmup_cosine"):
-            raise ValueError(f"lr_schedule={self.lr_schedule!r}: expected 'constant' or 'warmup_cosine'")
-        W, N, r = self.lr_warmup_steps, self.lr_decay_steps, self.lr_min_ratio
+        if self.lr_schedule not in _SCHEDULES:
+            raise ValueError(f"lr_schedule={self.lr_schedule!r}: expected one of {', '.join(map(repr, _SCHEDULES))}")
+        W, N, r, C = self.lr_warmup_steps, self.lr_decay_steps, self.lr_min_ratio, self.lr_cooldown_steps
         if isinstance(W, bool) or isinstance(N, bool) or int(W) != W or int(N) != N or W < 0 or N < 0:
             raise ValueError(f"lr_warmup_steps={W!r}, lr_decay_steps={N!r}: expected non-negative integers")
+        if isinstance(C, bool) or not isinstance(C, int) or C < 0:
+            raise ValueError(f"lr_cooldown_steps={C!r}: expected a non-negative integer")
         if not (0.0 <= float(r) <= 1.0):
             raise ValueError(f"lr_min_ratio={r!r}: expected a ratio in [0, 1]")
-        if self.lr_schedule == "warmup_cosine" and N <= W:
-            raise ValueError(f"lr_schedule=warmup_cosine needs lr_decay_steps > lr_warmup_steps (got N={N}, W={W}: "
-                             "N counts the warmup)")
+        if self.lr_schedule in ("warmup_cosine", "warmup_linear") and N <= W:
+            raise ValueError(f"lr_schedule={self.lr_schedule} needs lr_decay_steps > lr_warmup_steps (got N={N}, "
+                             f"W={W}: N counts the warmup)")
+        if self.lr_schedule == "wsd" and (C < 1 or W + C > N):
+            raise ValueError(f"lr_schedule=wsd needs lr_cooldown_steps >= 1 and lr_warmup_steps + lr_cooldown_steps <= "
+                             f"lr_decay_steps (got W={W}, C={C}, N={N})")
+        groups = self.param_groups
+        if groups is None:
+            groups = ()
+        if isinstance(groups, (dict, str, ParamGroup)) or not isinstance(groups, (list, tuple)):
+            raise ValueError(f"param_groups={groups!r}: expected a list of mappings")
+        object.__setattr__(self, "param_groups", tuple(_param_group(i, g) for i, g in enumerate(groups)))
 
     @property
     def scheduled(self) -> bool:
         return self.lr_schedule != "constant"
 
+    @property
+    def cooldown(self) -> int:
+        """C of the linear-decay schedules: ``lr_cooldown_steps`` for wsd, N - W for warmup_linear (which IS wsd with
+        that C: one arithmetic on the host and on the device)."""
+        if self.lr_schedule == "warmup_linear":
+            return int(self.lr_decay_steps) - int(self.lr_warmup_steps)
+        return int(self.lr_cooldown_steps) if self.lr_schedule == "wsd" else 0
+
     def lr_at(self, t: int) -> float:
         """The learning rate of update ``t`` (1-based: the already-incremented step counter) in float64.  optax
-        counts the updates already applied, c = t - 1: lr * c / W during warmup, then the cosine from lr down to
-        lr * r over the N - W steps that follow, then lr * r."""
+        counts the updates already applied, c = t - 1: lr * c / W during warmup, then either the cosine from lr down
+        to lr * r over the N - W steps that follow, or (wsd; warmup_linear = wsd with C = N - W) lr up to update
+        N - C and a straight line down to lr * r over the last C; lr * r from update N on."""
         import math
 
         if not self.scheduled:
@@ -165,13 +244,53 @@ class OptimConfig:
         c = int(t) - 1
         if c < W:
             return float(self.lr) * c / W
+        if self.lr_schedule in ("wsd", "warmup_linear"):
+            C = self.cooldown
+            if c < N - C:
+                return float(self.lr)
+            if c >= N:
+                return float(self.lr) * r
+            return float(self.lr) * (1.0 - (1.0 - r) * (c - (N - C)) / C)
         x = min(c - W, N - W) / (N - W)
         return float(self.lr) * (r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * x)))
 
     def schedule_key(self) -> str:
-        """What a checkpoint records so that a resume under other schedule fields is refused."""
-        return (f"{self.lr_schedule}:{int(self.lr_warmup_steps)}:{int(self.lr_decay_steps)}:"
-                f"{float(self.lr_min_ratio)!r}")
+        """What a checkpoint records so that a resume under other schedule fields is refused (the cooldown only for
+        the kinds that have one: the strings of constant and warmup_cosine are those of older checkpoints)."""
+        key = (f"{self.lr_schedule}:{int(self.lr_warmup_steps)}:{int(self.lr_decay_steps)}:"
+               f"{float(self.lr_min_ratio)!r}")
+        return f"{key}:{self.cooldown}" if self.lr_schedule in ("wsd", "warmup_linear") else key
+
+    # -- parameter groups ---------------------------------------------------------
+    def group_of(self, name: str) -> int:
+        """Index of the first group whose patterns match ``name``, or -1 (the global decay, scale 1)."""
+        for i, g in enumerate(self.param_groups):
+            if g.matches(name):
+                return i
+        return -1
+
+    def group_values(self, name: str) -> Tuple[float, float]:
+        """(weight_decay, lr_scale) of the parameter ``name``."""
+        i = self.group_of(name)
+        if i < 0:
+            return float(self.weight_decay), 1.0
+        g = self.param_groups[i]
+        return (float(self.weight_decay) if g.weight_decay is None else g.weight_decay,
+                1.0 if g.lr_scale is None else g.lr_scale)
+
+    def check_groups(self, names) -> None:
+        """Every pattern must match at least one of ``names`` (the whole model's parameter names): a typo would
+        otherwise silently leave its parameters in the default group."""
+        names = list(names)
+        for i, g in enumerate(self.param_groups):
+            for pat in g.match:
+                if not any(ParamGroup((pat,), 0.0).matches(n) for n in names):
+                    raise ValueError(f"param_groups[{i}]: pattern {pat!r} matches no parameter (names look like "
+                                     f"{', '.join(names[:4])}, ...)")
+
+    def groups_key(self) -> str:
+        """What a checkpoint records so that a resume under other groups is refused; '' when none is configured."""
+        return ";".join(f"{','.join(g.match)}|wd={g.weight_decay!r}|s={g.lr_scale!r}" for g in self.param_groups)
 
 
 @dataclass(frozen=True)
@@ -344,6 +463,6 @@ def build_configs(train_config_path: str, model_config_path: str = "configs/mode
 
 
 __all__ = [
-    "PyTree", "ModelConfig", "OptimConfig", "TrainConfig", "MODEL_PRESETS", "REFERENCE_VOCAB_SIZE",
+    "PyTree", "ModelConfig", "OptimConfig", "ParamGroup", "TrainConfig", "MODEL_PRESETS", "REFERENCE_VOCAB_SIZE",
     "model_config_from_preset", "build_configs", "load_yaml", "replace", "field",
 ]

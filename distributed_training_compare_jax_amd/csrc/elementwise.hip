@@ -588,14 +588,24 @@ __global__ void __launch_bounds__(256) sumsq_stage1(const float* __restrict__ x,
 // schedule from the counter instead of a rate frozen into a kernel argument.  optax's warmup_cosine_decay_schedule
 // (0 -> lr over `warmup` updates, a cosine down to lr * min_ratio at update `decay`, constant after) under
 // scale_by_schedule: the count is the number of updates already applied, t - 1 with the bumped counter t.
+// kind 1 (wsd; warmup_linear is wsd with cooldown = decay - warmup, set by the host): lr from update `warmup` to
+// update decay - cooldown, then a straight line down to lr * min_ratio at update `decay`, constant after.
 struct LrSched {
   float* out;      // null: no schedule (the AdamW kernels use their by-value lr)
   float lr, min_ratio;
   long warmup, decay;  // decay > warmup (host-checked)
+  int kind;            // 0: warmup_cosine, 1: wsd
+  long cooldown;       // wsd: 1 <= cooldown, warmup + cooldown <= decay (host-checked)
 };
 __device__ __forceinline__ float lr_schedule_at(const LrSched& s, int64_t t) {
   const long c = (long)t - 1;
   if (c < s.warmup) return s.lr * ((float)c / (float)s.warmup);
+  if (s.kind == 1) {
+    const long c0 = s.decay - s.cooldown;
+    if (c < c0) return s.lr;
+    if (c >= s.decay) return s.lr * s.min_ratio;
+    return s.lr * (1.f - (1.f - s.min_ratio) * ((float)(c - c0) / (float)s.cooldown));
+  }
   const long span = s.decay - s.warmup, k = c - s.warmup < span ? c - s.warmup : span;
   const float x = (float)k / (float)span;
   return s.lr * (s.min_ratio + (1.f - s.min_ratio) * (0.5f * (1.f + cospif(x))));
@@ -637,12 +647,34 @@ __global__ void sumsq_stage2(const float* __restrict__ part, int P, float* __res
 #ifndef DTC_ADAMW_CH
 #define DTC_ADAMW_CH 2
 #endif
-template <bool STRIDE, int CH>
+// Parameter groups (OptimConfig.param_groups): the flat buffer as `nruns` maximal runs of one (weight decay, rate
+// scale), in device memory, built once per FlatParams (ops/optim.py GroupTable).  Run r covers the flat offsets
+// [end[r - 1], end[r]) (end[-1] = 0) and hp[2r], hp[2r + 1] are its decay and scale; every bound is a multiple of 64
+// and every launch starts at a multiple of 4, so a thread's four elements lie in one run.  `base` is the flat
+// offset of the launch's element 0 (launches cover slices that begin and end inside runs).
+struct AwRuns {
+  const long* end;
+  const float* hp;
+  int nruns;
+  long base;
+};
+// first run whose end lies beyond `pos`, searched in [lo, nruns): with a block-uniform `pos` every operand is
+// uniform, so this runs once per block on the scalar unit
+__device__ __forceinline__ int aw_run_of(const AwRuns& R, long pos, int lo) {
+  int hi = R.nruns - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (pos < R.end[mid]) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+template <bool STRIDE, int CH, bool GROUPED = false>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, bf16* __restrict__ mirror, long n, long n_mirror,
                              const int64_t* __restrict__ step, const float* __restrict__ sumsq, float lr, float b1,
                              float b2, float eps, float wd, float max_norm, const float* __restrict__ enable,
-                             const float* __restrict__ lr_dev) {
+                             const float* __restrict__ lr_dev, AwRuns runs = AwRuns{}) {
   // CH 4-element groups per thread, 1024 elements apart (the per-thread clip / bias-correction
   // prologue — a sqrt, two powf and a division — amortised over 4*CH elements)
   long i = (long)blockIdx.x * blockDim.x * 4 * CH + threadIdx.x * 4;
@@ -654,11 +686,20 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
   if (lr_dev) lr = lr_dev[0];  // this update's scheduled rate (null: the by-value constant)
   const long stride = STRIDE ? (long)gridDim.x * blockDim.x * 4 * CH : n;
+  // GROUPED: the run of the block's first element, located once per block (and per grid-stride round) from
+  // block-uniform operands only
+  [[maybe_unused]] int run0 = 0;
+  [[maybe_unused]] long bpos = runs.base + (long)blockIdx.x * blockDim.x * 4 * CH;
   do {
     if (STRIDE && i >= n) break;
+    if constexpr (GROUPED) {
+      run0 = aw_run_of(runs, bpos, run0);
+      bpos += stride;
+    }
     // once-touched stream (2.7 GB per step): non-temporal loads/stores keep it out of L2/MALL
     // (measured 5.42 -> 5.345 ms/step)
     f32x4 pp[CH], gg[CH], mm[CH], vv[CH];
+    [[maybe_unused]] int run = 0;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       const long j = i + (long)c * blockDim.x * 4;
@@ -673,6 +714,15 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     for (int c = 0; c < CH; ++c) {
       const long j = i + (long)c * blockDim.x * 4;
       if (CH > 1 && j >= n) break;
+      // this element's hyper-parameters: the lanes step forward from the block's run (the chunks of a thread
+      // ascend, so `run` only ever advances); lr_c = lr (x) scale is ONE fp32 multiply, the identity at scale 1
+      float wd_c = wd, lr_c = lr;
+      if constexpr (GROUPED) {
+        if (c == 0) run = run0;
+        while (runs.base + j >= runs.end[run]) ++run;  // ends at the last run: its end covers base + n (host-checked)
+        wd_c = runs.hp[2 * run];
+        lr_c = lr * runs.hp[2 * run + 1];
+      }
       // explicit fmaf: no contraction left to the compiler, so every launch shape (full grid,
       // capped grid, any CH) rounds identically
 #pragma unroll
@@ -681,7 +731,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         mm[c][r] = fmaf(b1, mm[c][r], (1.f - b1) * gc);
         vv[c][r] = fmaf(b2, vv[c][r], ((1.f - b2) * gc) * gc);
         const float mh = mm[c][r] / bc1, vh = vv[c][r] / bc2;
-        pp[c][r] = fmaf(-lr, fmaf(wd, pp[c][r], mh / (sqrtf(vh) + eps)), pp[c][r]);
+        pp[c][r] = fmaf(-lr_c, fmaf(wd_c, pp[c][r], mh / (sqrtf(vh) + eps)), pp[c][r]);
       }
       __builtin_nontemporal_store(pp[c], (f32x4*)(p + j));
       __builtin_nontemporal_store(mm[c], (f32x4*)(m + j));
@@ -729,12 +779,14 @@ constexpr int AW_MAX_SEG = 96;
 struct AwSeg {
   long lo, n;   // flat range [lo, lo + n), 4-aligned
   int blk0, pad;
+  float wd, lr_scale;  // parameter groups (the GROUPED kernels): a segment lies in one run of the group table
 };
 struct AwSegs {
   int nseg, nblocks;
   AwSeg s[AW_MAX_SEG];
 };
 // element-wise update of the segments (the ranges without a transposed copy), 4 x 4 elements per thread
+template <bool GROUPED>
 __global__ void __launch_bounds__(256) adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v,
                                                         bf16* __restrict__ mirror, long n_mirror, AwSegs segs,
@@ -747,6 +799,11 @@ __global__ void __launch_bounds__(256) adamw_seg_kernel(float* __restrict__ p, c
   const AwSeg& S = segs.s[lo];
   float clip, bc1, bc2, lr;
   aw_prologue(h, clip, bc1, bc2, lr);
+  [[maybe_unused]] float wd = h.wd;
+  if constexpr (GROUPED) {  // the segment's own decay, and its scale on the rate: one fp32 multiply
+    wd = S.wd;
+    lr = lr * S.lr_scale;
+  }
   const long base = S.lo + (long)(blockIdx.x - S.blk0) * 256 * 16;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -755,7 +812,7 @@ __global__ void __launch_bounds__(256) adamw_seg_kernel(float* __restrict__ p, c
     DTC_ASSERT(j + 4 <= S.lo + S.n);
     f32x4 pp = __builtin_nontemporal_load((f32x4*)(p + j)), gg = __builtin_nontemporal_load((const f32x4*)(g + j));
     f32x4 mm = __builtin_nontemporal_load((f32x4*)(m + j)), vv = __builtin_nontemporal_load((f32x4*)(v + j));
-    adamw4(pp, gg, mm, vv, clip, bc1, bc2, lr, h.b1, h.b2, h.eps, h.wd);
+    adamw4(pp, gg, mm, vv, clip, bc1, bc2, lr, h.b1, h.b2, h.eps, GROUPED ? wd : h.wd);
     __builtin_nontemporal_store(pp, (f32x4*)(p + j));
     __builtin_nontemporal_store(mm, (f32x4*)(m + j));
     __builtin_nontemporal_store(vv, (f32x4*)(v + j));
@@ -768,12 +825,14 @@ struct AwtTask {
   long off;     // flat offset of the [rows][cols] weight (its mirror sits at the same offset)
   bf16* dst;    // W^T [cols][rows]
   int rows, cols, blk0, pad;
+  float wd, lr_scale;  // parameter groups (the GROUPED kernel): a weight is one parameter, hence one group
 };
 struct AwtBatch {
   int ntasks, nblocks;
   AwtTask t[AWT_MAX];
 };
 // 64 x 64 tiles of the transposed-mirror weights: update, mirror, and W^T through an LDS tile
+template <bool GROUPED>
 __global__ void __launch_bounds__(256) adamw_tr_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v,
                                                        bf16* __restrict__ mirror, AwtBatch b, AwHyper h) {
@@ -789,6 +848,11 @@ __global__ void __launch_bounds__(256) adamw_tr_kernel(float* __restrict__ p, co
   __shared__ bf16 tile[64][64 + 1];  // row length 65: the column reads below spread over the banks
   float clip, bc1, bc2, lr;
   aw_prologue(h, clip, bc1, bc2, lr);
+  [[maybe_unused]] float wd = h.wd;
+  if constexpr (GROUPED) {
+    wd = T.wd;
+    lr = lr * T.lr_scale;
+  }
   const int tid = threadIdx.x;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {  // 64 rows x 16 groups of 4 columns: a row is 16 lanes x 16 B
@@ -798,7 +862,7 @@ __global__ void __launch_bounds__(256) adamw_tr_kernel(float* __restrict__ p, co
       const long j = T.off + (long)(r0 + r) * T.cols + c0 + c4;
       f32x4 pp = __builtin_nontemporal_load((f32x4*)(p + j)), gg = __builtin_nontemporal_load((const f32x4*)(g + j));
       f32x4 mm = __builtin_nontemporal_load((f32x4*)(m + j)), vv = __builtin_nontemporal_load((f32x4*)(v + j));
-      adamw4(pp, gg, mm, vv, clip, bc1, bc2, lr, h.b1, h.b2, h.eps, h.wd);
+      adamw4(pp, gg, mm, vv, clip, bc1, bc2, lr, h.b1, h.b2, h.eps, GROUPED ? wd : h.wd);
       __builtin_nontemporal_store(pp, (f32x4*)(p + j));
       __builtin_nontemporal_store(mm, (f32x4*)(m + j));
       __builtin_nontemporal_store(vv, (f32x4*)(v + j));
@@ -1043,22 +1107,31 @@ long dtc_sumsq_workspace_bytes() { return SS_BLOCKS * 4; }
 
 // `lr_out` non-null: the finishing thread also writes the scheduled rate of the bumped step (LrSched)
 static int lr_sched_make(LrSched& s, float* lr_out, float lr, float min_ratio, long warmup, long decay,
-                         const int64_t* step) {
-  s = LrSched{lr_out, lr, min_ratio, warmup, decay};
-  if (lr_out && (!step || warmup < 0 || decay <= warmup || !(min_ratio >= 0.f && min_ratio <= 1.f))) return 3012;
+                         const int64_t* step, int kind = 0, long cooldown = 0) {
+  s = LrSched{lr_out, lr, min_ratio, warmup, decay, kind, cooldown};
+  if (!lr_out) return 0;
+  if (!step || warmup < 0 || !(min_ratio >= 0.f && min_ratio <= 1.f)) return 3012;
+  if (kind == 0 ? decay <= warmup : (kind != 1 || cooldown < 1 || warmup + cooldown > decay)) return 3012;
   return 0;
 }
 
-int dtc_sumsq_segments_lr(const float* x, const double* seg, int S, float* out, int64_t* step, float* ws, long ws_bytes,
-                          float* lr_out, float lr, float min_ratio, long warmup, long decay, hipStream_t st) {
+// `kind` / `cooldown`: LrSched (0: warmup_cosine, 1: wsd)
+int dtc_sumsq_segments_sched(const float* x, const double* seg, int S, float* out, int64_t* step, float* ws,
+                             long ws_bytes, float* lr_out, float lr, float min_ratio, long warmup, long decay, int kind,
+                             long cooldown, hipStream_t st) {
   if (ws_bytes < SS_BLOCKS * 4) return 3004;
   LrSched sched;
-  if (int rc = lr_sched_make(sched, lr_out, lr, min_ratio, warmup, decay, step)) return rc;
+  if (int rc = lr_sched_make(sched, lr_out, lr, min_ratio, warmup, decay, step, kind, cooldown)) return rc;
   hipLaunchKernelGGL(sumsq_stage1, dim3(SS_BLOCKS), dim3(256), 0, st, x, seg, S, ws);
   DTC_CHECK_LAUNCH();
   hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(1024), 0, st, ws, SS_BLOCKS, out, step, sched);
   DTC_CHECK_LAUNCH();
   return 0;
+}
+
+int dtc_sumsq_segments_lr(const float* x, const double* seg, int S, float* out, int64_t* step, float* ws, long ws_bytes,
+                          float* lr_out, float lr, float min_ratio, long warmup, long decay, hipStream_t st) {
+  return dtc_sumsq_segments_sched(x, seg, S, out, step, ws, ws_bytes, lr_out, lr, min_ratio, warmup, decay, 0, 0, st);
 }
 
 int dtc_sumsq_segments(const float* x, const double* seg, int S, float* out, int64_t* step, float* ws, long ws_bytes,
@@ -1075,13 +1148,18 @@ int dtc_sumsq_partial(const float* x, const double* seg, int S, float* part, int
   return 0;
 }
 
-int dtc_sum_finish_lr(const float* part, int P, float* out, int64_t* step, float* lr_out, float lr, float min_ratio,
-                      long warmup, long decay, hipStream_t st) {
+int dtc_sum_finish_sched(const float* part, int P, float* out, int64_t* step, float* lr_out, float lr, float min_ratio,
+                         long warmup, long decay, int kind, long cooldown, hipStream_t st) {
   LrSched sched;
-  if (int rc = lr_sched_make(sched, lr_out, lr, min_ratio, warmup, decay, step)) return rc;
+  if (int rc = lr_sched_make(sched, lr_out, lr, min_ratio, warmup, decay, step, kind, cooldown)) return rc;
   hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(1024), 0, st, part, P, out, step, sched);
   DTC_CHECK_LAUNCH();
   return 0;
+}
+
+int dtc_sum_finish_lr(const float* part, int P, float* out, int64_t* step, float* lr_out, float lr, float min_ratio,
+                      long warmup, long decay, hipStream_t st) {
+  return dtc_sum_finish_sched(part, P, out, step, lr_out, lr, min_ratio, warmup, decay, 0, 0, st);
 }
 
 int dtc_sum_finish(const float* part, int P, float* out, int64_t* step, hipStream_t st) {
@@ -1103,6 +1181,26 @@ int dtc_adamw_lr(float* p, const float* g, float* m, float* v, bf16* mirror, lon
   return 0;
 }
 
+// Parameter groups: `run_end` (long [nruns], ascending multiples of 64) and `run_hp` (float [nruns][2]: decay, rate
+// scale) in device memory, `base` the flat offset of p[0].  The table must cover [base, base + n).
+int dtc_adamw_groups(float* p, const float* g, float* m, float* v, bf16* mirror, long n, long n_mirror,
+                     const int64_t* step, const float* sumsq, float lr, float b1, float b2, float eps, float wd,
+                     float max_norm, const float* enable, int max_blocks, const float* lr_dev, const long* run_end,
+                     const float* run_hp, int nruns, long base, long table_end, hipStream_t st) {
+  if (n % 4 || n_mirror % 4 || base % 4) return 3005;
+  if (!run_end || !run_hp || nruns < 1 || base < 0 || base + n > table_end) return 3013;
+  const AwRuns runs{run_end, run_hp, nruns, base};
+  const long blocks = blocks_for(n / 4, 256 * DTC_ADAMW_CH);
+  if (max_blocks > 0 && blocks > max_blocks)
+    hipLaunchKernelGGL((adamw_kernel<true, DTC_ADAMW_CH, true>), dim3(max_blocks), dim3(256), 0, st, p, g, m, v, mirror, n,
+                       n_mirror, step, sumsq, lr, b1, b2, eps, wd, max_norm, enable, lr_dev, runs);
+  else
+    hipLaunchKernelGGL((adamw_kernel<false, DTC_ADAMW_CH, true>), dim3(blocks), dim3(256), 0, st, p, g, m, v, mirror, n,
+                       n_mirror, step, sumsq, lr, b1, b2, eps, wd, max_norm, enable, lr_dev, runs);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
 int dtc_adamw(float* p, const float* g, float* m, float* v, bf16* mirror, long n, long n_mirror, const int64_t* step,
               const float* sumsq, float lr, float b1, float b2, float eps, float wd, float max_norm,
               const float* enable, int max_blocks, hipStream_t st) {
@@ -1115,9 +1213,10 @@ int dtc_aw_max_seg() { return AW_MAX_SEG; }
 int dtc_aw_max_tasks() { return AWT_MAX; }
 int dtc_aw_seg_bytes() { return (int)sizeof(AwSeg); }
 int dtc_aw_task_bytes() { return (int)sizeof(AwtTask); }
-int dtc_adamw_tr_lr(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,
-                    const AwtBatch* tasks, const int64_t* step, const float* sumsq, float lr, float b1, float b2,
-                    float eps, float wd, float max_norm, const float* lr_dev, hipStream_t st) {
+// `grouped`: every segment and task carries its own (wd, lr_scale) (the plan was split at the group table's runs)
+static int adamw_tr_launch(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,
+                           const AwtBatch* tasks, const int64_t* step, const float* sumsq, float lr, float b1, float b2,
+                           float eps, float wd, float max_norm, const float* lr_dev, bool grouped, hipStream_t st) {
   if (segs->nseg > AW_MAX_SEG || tasks->ntasks > AWT_MAX || n_mirror % 4) return 3005;
   for (int i = 0; i < segs->nseg; ++i)
     if (segs->s[i].lo % 4 || segs->s[i].n % 4) return 3005;
@@ -1125,14 +1224,34 @@ int dtc_adamw_tr_lr(float* p, const float* g, float* m, float* v, bf16* mirror, 
     if (tasks->t[i].rows % 8 || tasks->t[i].cols % 4 || tasks->t[i].off % 4) return 3011;
   const AwHyper h{step, sumsq, lr, b1, b2, eps, wd, max_norm, lr_dev};
   if (segs->nseg > 0 && segs->nblocks > 0) {
-    hipLaunchKernelGGL(adamw_seg_kernel, dim3(segs->nblocks), dim3(256), 0, st, p, g, m, v, mirror, n_mirror, *segs, h);
+    if (grouped)
+      hipLaunchKernelGGL(adamw_seg_kernel<true>, dim3(segs->nblocks), dim3(256), 0, st, p, g, m, v, mirror, n_mirror, *segs, h);
+    else
+      hipLaunchKernelGGL(adamw_seg_kernel<false>, dim3(segs->nblocks), dim3(256), 0, st, p, g, m, v, mirror, n_mirror, *segs, h);
     DTC_CHECK_LAUNCH();
   }
   if (tasks->ntasks > 0 && tasks->nblocks > 0) {
-    hipLaunchKernelGGL(adamw_tr_kernel, dim3(tasks->nblocks), dim3(256), 0, st, p, g, m, v, mirror, *tasks, h);
+    if (grouped)
+      hipLaunchKernelGGL(adamw_tr_kernel<true>, dim3(tasks->nblocks), dim3(256), 0, st, p, g, m, v, mirror, *tasks, h);
+    else
+      hipLaunchKernelGGL(adamw_tr_kernel<false>, dim3(tasks->nblocks), dim3(256), 0, st, p, g, m, v, mirror, *tasks, h);
     DTC_CHECK_LAUNCH();
   }
   return 0;
+}
+
+int dtc_adamw_tr_lr(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,
+                    const AwtBatch* tasks, const int64_t* step, const float* sumsq, float lr, float b1, float b2,
+                    float eps, float wd, float max_norm, const float* lr_dev, hipStream_t st) {
+  return adamw_tr_launch(p, g, m, v, mirror, n_mirror, segs, tasks, step, sumsq, lr, b1, b2, eps, wd, max_norm, lr_dev,
+                         false, st);
+}
+
+int dtc_adamw_tr_groups(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,
+                        const AwtBatch* tasks, const int64_t* step, const float* sumsq, float lr, float b1, float b2,
+                        float eps, float wd, float max_norm, const float* lr_dev, hipStream_t st) {
+  return adamw_tr_launch(p, g, m, v, mirror, n_mirror, segs, tasks, step, sumsq, lr, b1, b2, eps, wd, max_norm, lr_dev,
+                         true, st);
 }
 
 int dtc_adamw_tr(float* p, const float* g, float* m, float* v, bf16* mirror, long n_mirror, const AwSegs* segs,

@@ -179,6 +179,10 @@ def _declare(lib):
         "dtc_sum_finish": ([vp, i, vp, vp, vp], i),
         "dtc_sumsq_segments_lr": ([vp, vp, i, vp, vp, vp, l, vp, f, f, l, l, vp], i),
         "dtc_sum_finish_lr": ([vp, i, vp, vp, vp, f, f, l, l, vp], i),
+        "dtc_sumsq_segments_sched": ([vp, vp, i, vp, vp, vp, l, vp, f, f, l, l, i, l, vp], i),
+        "dtc_sum_finish_sched": ([vp, i, vp, vp, vp, f, f, l, l, i, l, vp], i),
+        "dtc_adamw_groups": ([vp, vp, vp, vp, vp, l, l, vp, vp, f, f, f, f, f, f, vp, i, vp, vp, vp, i, l, l, vp], i),
+        "dtc_adamw_tr_groups": ([vp, vp, vp, vp, vp, l, vp, vp, vp, vp, f, f, f, f, f, f, vp, vp], i),
         "dtc_adamw_lr": ([vp, vp, vp, vp, vp, l, l, vp, vp, f, f, f, f, f, f, vp, i, vp, vp], i),
         "dtc_adamw_tr_lr": ([vp, vp, vp, vp, vp, l, vp, vp, vp, vp, f, f, f, f, f, f, vp, vp], i),
         "dtc_adamw": ([vp, vp, vp, vp, vp, l, l, vp, vp, f, f, f, f, f, f, vp, i, vp], i),

@@ -41,6 +41,12 @@ class Engine:
         self.dinfo = dinfo
         self.device = dinfo.device
         dp, tp, pp = resolve_degrees(train_cfg.parallel, dinfo.world, train_cfg.dp, train_cfg.tp, train_cfg.pp)
+        # param_groups: every pattern must name a parameter of the WHOLE model (a stage holds only some), checked
+        # here, before any collective, so every rank raises alike on a typo
+        if opt_cfg.param_groups:
+            from ..models.params import all_param_specs
+
+            opt_cfg.check_groups([sp.name for sp in all_param_specs(model_cfg)])
         # pp_comm: p2p (the stage messages, the PP loss sum and the pp_clip: global norm as in-graph kernels over
         # IPC-mapped buffers, parallel/p2p.py P2PPipe): what it does not cover is refused here, before any collective
         if train_cfg.pp_comm not in ("rccl", "p2p"):

@@ -167,6 +167,8 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
                   grad_accum=eng.grad_accum, microbatch_rows=eng.mb_rows,
                   lr_schedule=opt_config.lr_schedule)
     result["tflops_per_gpu"] = result["tflops"] / max(1, dinfo.world)
+    if opt_config.param_groups:
+        result["param_groups"] = len(opt_config.param_groups)
     if train_config.eval_every:
         last = evals[-1][2] if evals else None
         result.update(eval_last=None if last is None else dict(step=evals[-1][0], **last), eval_time_total_s=eval_s)

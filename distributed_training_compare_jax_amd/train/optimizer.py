@@ -45,6 +45,28 @@ def merge_segments(segs, total: int):
     return out
 
 
+def group_table(flat: FlatParams, cfg: OptimConfig):
+    """The :class:`ops.optim.GroupTable` of ``flat`` under ``cfg.param_groups`` (None when no group is configured):
+    one run per maximal range of equal (weight decay, rate scale), alignment gaps absorbed as in
+    :func:`merge_segments`.  Built from the specs ``flat`` holds, so a pipeline stage's table is the restriction of
+    the whole model's.  Cached on ``flat`` (one table per buffer, built before any capture)."""
+    if not getattr(cfg, "param_groups", ()):
+        return None
+    cached = getattr(flat, "_group_table", None)
+    if cached is not None and cached[0] == cfg.groups_key() + f"|{cfg.weight_decay!r}":
+        return cached[1]
+    ids = {}  # distinct (wd, scale) -> id: two groups with equal values share runs
+    key = lambda spec: float(ids.setdefault(cfg.group_values(spec.name), len(ids)))
+    segs = flat.segments(key)
+    first = min(o for o, _, _ in segs)
+    assert first == 0, "the first slot starts the flat buffer"
+    vals = {float(i): v for v, i in ids.items()}
+    runs = [(o, o + n, *vals[w]) for o, n, w in merge_segments(segs, flat.numel)]
+    table = O.GroupTable(runs, flat.numel, flat.device)
+    flat._group_table = (cfg.groups_key() + f"|{cfg.weight_decay!r}", table)
+    return table
+
+
 def _subtract_ranges(segs, ranges):
     """``segs`` [(offset, n, weight)] minus the flat ranges [(offset, n)] (sorted, disjoint)."""
     out = []
@@ -65,6 +87,15 @@ def _subtract_ranges(segs, ranges):
     return out
 
 
+def _gkw(groups, base: int) -> dict:
+    """The keyword arguments of a grouped ``adamw_flat`` launch whose slice starts at flat offset ``base`` (none
+    without groups: the ungrouped entry points)."""
+    if groups is None:
+        return {}
+    assert base % 4 == 0, f"an AdamW launch starts at a 4-aligned flat offset (got {base})"
+    return dict(groups=groups, base=int(base))
+
+
 class FusedAdamW:
     def __init__(self, flat: FlatParams, cfg: OptimConfig, program, tp_size: int = 1, tp_group=None,
                  pp_group=None, pp_global_clip: bool = False):
@@ -72,6 +103,7 @@ class FusedAdamW:
         self.cfg = cfg
         self.program = program
         self._aw_plans = {}  # (lo, hi) -> fused AdamW + transpose launch lists
+        self.groups = group_table(flat, cfg)  # param_groups: per-run (wd, lr scale), or None
         self.tp_size, self.tp_group = tp_size, tp_group
         self.pp_group = pp_group if pp_global_clip else None
         dev = flat.device
@@ -199,6 +231,7 @@ class FusedAdamW:
         """Clip + AdamW over flat[lo:hi] (4-aligned) with the norm/step of the last :meth:`norm`
         (skipped on device when ``enable[0] == 0``; ``max_blocks`` caps the kernel's grid)."""
         f, c = self.flat, self.cfg
+        assert lo % 4 == 0 and hi % 4 == 0, (lo, hi)
         if hi <= lo:
             return
         nm = (min(max(f.n_mirror - lo, 0), hi - lo) if f.use_mirror else 0)
@@ -206,7 +239,8 @@ class FusedAdamW:
             # the transposed mirror written by the update itself (ops/optim.py adamw_tr)
             key = (lo, hi)
             if key not in self._aw_plans:
-                self._aw_plans[key] = O.adamw_tr_plan(lo, hi, f.transposed_in(lo, hi))
+                self._aw_plans[key] = (O.adamw_tr_plan(lo, hi, f.transposed_in(lo, hi)) if self.groups is None else
+                                       O.adamw_tr_plan(lo, hi, f.transposed_in(lo, hi), groups=self.groups))
             plan = self._aw_plans[key]
             if plan is not None:
                 O.adamw_tr(f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.mirror, f.n_mirror, plan, self.step_t,
@@ -218,7 +252,7 @@ class FusedAdamW:
         O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[lo:hi], f.exp_avg_sq[lo:hi],
                      f.mirror[lo:lo + max(nm, 4)] if nm > 0 else None, nm, self.step_t, self.sumsq, c.lr, c.b1, c.b2,
                      c.eps, c.weight_decay, c.grad_clip, enable=enable, max_blocks=max_blocks,
-                     lr_dev=O._lr_dev(self.sched))
+                     lr_dev=O._lr_dev(self.sched), **_gkw(self.groups, lo))
         if nm > 0:
             f.refresh_transposed(lo, hi)
         f.refresh_fp8(lo, hi)
@@ -278,6 +312,7 @@ class P2PShardedAdamW:
         self.sumsq = self._sq4[:1]
         self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
         self.sched = O.LrSchedule.of(cfg, dev)  # lr_schedule: the rate of each update, written with the step bump
+        self.groups = group_table(flat, cfg)  # param_groups: the owned pieces begin and end inside its runs
         self.reducer = None
         self.peer = None
         self.plan_hash = None
@@ -305,7 +340,8 @@ class P2PShardedAdamW:
             if hi > lo:
                 O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[off:off + hi - lo],
                              f.exp_avg_sq[off:off + hi - lo], None, 0, self.step_t, self.sumsq, c.lr, c.b1, c.b2,
-                             c.eps, c.weight_decay, c.grad_clip, lr_dev=O._lr_dev(self.sched))
+                             c.eps, c.weight_decay, c.grad_clip, lr_dev=O._lr_dev(self.sched),
+                             **_gkw(self.groups, lo))
         nm = f.n_mirror if f.use_mirror else 0
 
         def gathers():
@@ -370,6 +406,7 @@ class ShardedAdamW:
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
         self.sched = O.LrSchedule.of(cfg, dev)  # lr_schedule: the rate of each update, written with the step bump
+        self.groups = group_table(flat, cfg)  # param_groups: the slice [lo, hi) begins and ends inside its runs
         self.reducer = None
         # gloo on device tensors (the 2-ranks-on-one-GPU test rig) lacks the in-place tensor
         # collectives: emulate them with all_reduce / list all_gather (same results)
@@ -381,7 +418,7 @@ class ShardedAdamW:
             return
         O.adamw_flat(f.params[lo:hi], f.grads[lo:hi], f.exp_avg[mlo:mlo + hi - lo], f.exp_avg_sq[mlo:mlo + hi - lo],
                      None, 0, self.step_t, self.sumsq, c.lr, c.b1, c.b2, c.eps, c.weight_decay, c.grad_clip,
-                     lr_dev=O._lr_dev(self.sched))
+                     lr_dev=O._lr_dev(self.sched), **_gkw(self.groups, lo))
 
     def step(self):
         if self.reducer is not None:

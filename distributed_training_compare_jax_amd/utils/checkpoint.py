@@ -48,7 +48,7 @@ def save(eng, output_dir: str, step: int):
     meta = dict(step=step, dp=m.dp, tp=m.tp, pp=m.pp, rank=m.rank, dp_idx=m.dp_idx, tp_idx=m.tp_idx,
                 pp_idx=m.pp_idx, slots=slots, model=eng.mcfg.name,
                 zero_stage=int(getattr(eng, "zero", False)), **_zero_meta(eng),
-                lr_schedule=eng.ocfg.schedule_key(),
+                lr_schedule=eng.ocfg.schedule_key(), param_groups=eng.ocfg.groups_key(),
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
                 vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab))
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
@@ -125,6 +125,11 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
     if sched_ck != sched_now:
         raise ValueError(f"checkpoint was written under lr_schedule {sched_ck} (name:warmup:decay:min_ratio), this run "
                          f"has {sched_now}: resume with the schedule fields that wrote it")
+    # likewise the decay and the rate scale of every parameter (checkpoints from before the field: no groups)
+    groups_ck, groups_now = m0.get("param_groups", ""), eng.ocfg.groups_key()
+    if groups_ck != groups_now:
+        raise ValueError(f"checkpoint was written under param_groups {groups_ck!r}, this run has {groups_now!r} "
+                         "(patterns|wd|lr_scale per group): resume with the groups that wrote it")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
     for r, m in metas.items():
