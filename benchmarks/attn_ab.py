@@ -53,9 +53,9 @@ def main():
     o, lse = A.attn_fwd(qkv, H)
     fwd_flops = 4.0 * B * H * T * T * hd / 2  # causal: half of QK^T and PV
     if a.shape == "ref":
-        variants = {"fwd": lambda: A.attn_fwd(qkv, H), "fwd plain order": lambda: A.attn_fwd(qkv, H, flags=1),
+        variants = {"fwd": lambda: A.attn_fwd(qkv, H), "fwd plain order": lambda: A.attn_fwd(qkv, H, flags=A.FwdFlags.PLAIN_WAVES),
                     "bwd fused": lambda: A.attn_bwd(qkv, o, lse, do, H),
-                    "bwd two-round": lambda: A.attn_bwd(qkv, o, lse, do, H, flags=1)}
+                    "bwd two-round": lambda: A.attn_bwd(qkv, o, lse, do, H, flags=A.BwdFlags.TWO_ROUND)}
     elif a.shape == "hd128":
         H64 = 2 * H  # the yardstick: same d_model, FLOPs and bytes at head_dim 64 (same buffers, re-viewed)
         o64, lse64 = A.attn_fwd(qkv, H64)
@@ -63,28 +63,28 @@ def main():
                     "bwd hd128": lambda: A.attn_bwd(qkv, o, lse, do, H),
                     "bwd hd64 (H x 2)": lambda: A.attn_bwd(qkv, o64, lse64, do, H64)}
     else:
-        o4, _ = A.attn_fwd(qkv, H, flags=4)
-        o5, lse5 = A.attn_fwd(qkv, H, flags=16)
+        o4, _ = A.attn_fwd(qkv, H, flags=A.FwdFlags.CHUNK16)
+        o5, lse5 = A.attn_fwd(qkv, H, flags=A.FwdFlags.ROUND4)
         torch.cuda.synchronize()
         print(f"fwd 32-row vs 16-row kernel: max |do| {(o.float() - o4.float()).abs().max().item():.3e}", flush=True)
         print(f"fwd round-4 32-row kernel vs round-5 default: max |do| {(o.float() - o5.float()).abs().max().item():.3e} "
               f"max |dlse| {(lse - lse5).abs().max().item():.3e}", flush=True)
-        o6, lse6 = A.attn_fwd(qkv, H, flags=32)
+        o6, lse6 = A.attn_fwd(qkv, H, flags=A.FwdFlags.WPS2)
         torch.cuda.synchronize()
         print(f"fwd 2 waves/SIMD vs default (3): max |do| {(o.float() - o6.float()).abs().max().item():.3e} "
               f"max |dlse| {(lse - lse6).abs().max().item():.3e}", flush=True)
-        o7, lse7 = A.attn_fwd(qkv, H, flags=64)
+        o7, lse7 = A.attn_fwd(qkv, H, flags=A.FwdFlags.HEAVY_FIRST)
         torch.cuda.synchronize()
         print(f"fwd heavy-first vs CU-balanced (default) order: max |do| {(o.float() - o7.float()).abs().max().item():.3e} "
               f"max |dlse| {(lse - lse7).abs().max().item():.3e}", flush=True)
         variants = {"fwd (default, 3 waves/SIMD)": lambda: A.attn_fwd(qkv, H),
-                    "fwd heavy-first order": lambda: A.attn_fwd(qkv, H, flags=64),
-                    "fwd (2 waves/SIMD, round 5)": lambda: A.attn_fwd(qkv, H, flags=32),
-                    "fwd (round 4: 32 q/wave)": lambda: A.attn_fwd(qkv, H, flags=16),
-                    "fwd (16 q/wave chunk)": lambda: A.attn_fwd(qkv, H, flags=4),
+                    "fwd heavy-first order": lambda: A.attn_fwd(qkv, H, flags=A.FwdFlags.HEAVY_FIRST),
+                    "fwd (2 waves/SIMD, round 5)": lambda: A.attn_fwd(qkv, H, flags=A.FwdFlags.WPS2),
+                    "fwd (round 4: 32 q/wave)": lambda: A.attn_fwd(qkv, H, flags=A.FwdFlags.ROUND4),
+                    "fwd (16 q/wave chunk)": lambda: A.attn_fwd(qkv, H, flags=A.FwdFlags.CHUNK16),
                     "bwd (32 rows/wave)": lambda: A.attn_bwd(qkv, o, lse, do, H),
-                    "bwd merged (delta + 1 launch)": lambda: A.attn_bwd(qkv, o, lse, do, H, flags=8),
-                    "bwd (16-row chunk)": lambda: A.attn_bwd(qkv, o, lse, do, H, flags=4)}
+                    "bwd merged (delta + 1 launch)": lambda: A.attn_bwd(qkv, o, lse, do, H, flags=A.BwdFlags.FORCE_MERGED),
+                    "bwd (16-row chunk)": lambda: A.attn_bwd(qkv, o, lse, do, H, flags=A.BwdFlags.CHUNK16)}
     res = {k: [] for k in variants}
     for _ in range(a.rounds):
         for k, fn in variants.items():

@@ -15,9 +15,8 @@
 // one workgroup per 64-key block sweeping the queries; dQ with one workgroup per 64-query
 // block sweeping the keys.  P is recomputed from the saved LSE.
 #include "common.h"
-#include <vector>
+#include "attn_plan.h"
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -251,13 +250,6 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(const bf16* __restrict_
   if (ok && part == 0) delta[i] = s;
 }
 
-template <int HD>
-static void launch_attn_delta(const bf16* o, const bf16* dout, float* delta, int B, int T, int H, hipStream_t st) {
-  const long threads = (long)B * T * H * (HD / 8);
-  hipLaunchKernelGGL(attn_delta_kernel<HD>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, o, dout, delta,
-                     B, T, H);
-}
-
 // dK, dV: workgroup = (b, h, 64-key block); wave w owns keys kb*64+16w..+15 (key on the lane).
 template <int HD>
 __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
@@ -413,8 +405,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const bf16* __restrict
 // (23 us fwd / 60 us bwd at the reference shape).  Two 1024-thread blocks per (b, h), wave w of
 // block s owning 16-row group 2w+s, so causal work is balanced across the pair and each SIMD
 // interleaves 4 waves.
-constexpr int RES_THREADS = 1024;
-constexpr int RES_MAXT = 512;  // 16 waves x 2 blocks x 16 rows
+using ap::RES_THREADS;  // launch geometry the plan shares: csrc/attn_plan.h
+using ap::RES_MAXT;
 
 // max / sum over the 4 lane groups (lanes j, j+16, j+32, j+48) with the gfx950 row swaps instead
 // of ds_bpermute round trips through LDS
@@ -568,7 +560,9 @@ __global__ void __launch_bounds__(RES_THREADS) attn_fwd_res_kernel(const bf16* _
 // one barrier per 128 keys shared by 16 waves (the 256-thread tiled kernel pays a barrier and a
 // K/V load per 64 keys per 4 waves, and was latency-bound at ~25 TF/s).  Each wave skips the
 // 64-key tiles past its rows and masks only the tiles that cross its diagonal.
-constexpr int CH_THREADS = 1024, CH_KEYS = 128, CH_QROWS = 256;
+using ap::CH_THREADS;
+using ap::CH_QROWS;
+constexpr int CH_KEYS = 128;
 template <int HD>
 __host__ __device__ constexpr int ch_lds_fwd() { return 2 * CH_KEYS * (AttnLds<HD>::KLD + AttnLds<HD>::VLD) * 2; }
 
@@ -692,7 +686,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-constexpr int FW_THREADS = 256, FW_QROWS = 128, FW_KEYS = 64;
+using ap::FW_THREADS;
+using ap::FW_QROWS;
+constexpr int FW_KEYS = 64;
 constexpr float FW_THR = 8.f;
 template <int HD>
 struct FwLds {
@@ -941,17 +937,13 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
 // before its PV MFMAs instead of all at once after QK^T -- 154 instead of 178 VGPRs, so three 4-wave blocks
 // share a CU (768 blocks = one round at GPT-2 small) and the extra wave per SIMD covers the tile's serial
 // QK^T -> softmax -> PV chain: 27.21 -> 26.54 us per layer, bitwise identical (profiles/r6_attn_fwd_wps3.log;
-// 4 waves/SIMD spills 38 VGPRs).  flags bit 5 = the 2-wave form (A/B).
+// 4 waves/SIMD spills 38 VGPRs).  ap::FWD_WPS2 = the 2-wave form (A/B).
 // CU-balanced block order of a grid that is exactly one round (every block resident from the start): block
 // bid runs on XCD bid % 8 as that XCD's k = bid / 8-th block, and blocks k, k + C, k + 2C, ... of an XCD
 // (C = CUs per XCD) share a CU.  The host assigns the query blocks to those CU slots by longest-processing-
 // time-first (per-CU causal work within 1 unit instead of 17 vs 10 units of the heavy-first order at GPT-2
 // small): q[k] = query block, j[k] = which of its (b, h) on this XCD (bh = 8 j + XCD).  n = 0: heavy-first.
-constexpr int FW_ORDER_MAX = 256;
-struct FwOrder {
-  int n;
-  unsigned char q[FW_ORDER_MAX], j[FW_ORDER_MAX];
-};
+// (struct FwOrder and the host function that fills it, fw_order: csrc/attn_plan.h)
 
 template <int HD, int WPS = 3>
 __global__ void __launch_bounds__(FW_THREADS, WPS) attn_fwd5_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
@@ -1481,7 +1473,8 @@ __host__ __device__ constexpr int ch_lds_bwd() { return 4 * CH_KEYS * AttnLds<HD
 
 // dK, dV: block = (b, h, NTH/4 keys); wave w owns keys kb0 + 16w .. +15 (key on the lane).  512
 // threads: the dk/dv/p/ds accumulators spill at the 128 VGPRs of a 1024-thread block (hd 64)
-constexpr int CHB_THREADS = 512, CHB_KROWS = CHB_THREADS / 4;
+using ap::CHB_THREADS;
+using ap::CHB_KROWS;
 template <int HD>
 __global__ void __launch_bounds__(CHB_THREADS) attn_bwd_dkdv_chunk_kernel(
     const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const float* __restrict__ lse,
@@ -1921,7 +1914,7 @@ __global__ void __launch_bounds__(RES_THREADS) attn_bwd_dq_res_kernel(
 // rows (dK/dV query tiles start at 16-row offsets) and every row >= T is zero: there p = 2^0 = 1
 // but dO = 0 and delta = 0, so dV and dK receive exactly 0 from them — no bounds masks in the loops.
 // The causal mask is needed only on the diagonal tile, which is peeled (DIAG template).
-constexpr int FB_THREADS = 1024;
+using ap::FB_THREADS;
 constexpr int FB_MAXT_Q = RES_MAXT + 64;  // Q/dO panel rows at T = RES_MAXT
 
 __device__ __forceinline__ int fb_swz(int r) { return (0x1320 >> (((r >> 2) & 3) * 4)) & 3; }
@@ -2004,8 +1997,8 @@ __device__ __forceinline__ void fb_dq_tile(const bf16* sK, const bf16* sV, int k
 
 // rows of the Q/dO panels (and lse/delta) the fused backward stages: the dK/dV query tiles of the
 // last key group reach row 16*(ngroups-1) + 63
-__host__ __device__ inline int fb_rows_q(int T) { return (T + 15) / 16 * 16 + 64; }
-__host__ __device__ inline int fb_rows_k(int T) { return (T + 63) / 64 * 64; }
+using ap::fb_rows_q;  // csrc/attn_plan.h: the plan sizes the kernel's LDS from the same two functions
+using ap::fb_rows_k;
 
 template <int HD>
 __global__ void __launch_bounds__(FB_THREADS) attn_bwd_fused_kernel(
@@ -2133,33 +2126,95 @@ __global__ void __launch_bounds__(FB_THREADS) attn_bwd_fused_kernel(
   }
 }
 
+// ============================================================================ host: plan, launch, record
+// Which kernels a call runs is decided in csrc/attn_plan.h (plan_attn_fwd / plan_attn_bwd); what follows adds the
+// LDS sizes that come from the device layout structs above, launches from the plan and records it.
+static_assert(AttnLds<32>::KLD == ap::RES_KLD, "res_lds_fwd sizes the resident forward's K rows");
+static_assert(2 * (2 * sw_stage<128>() * 2) <= ap::LDS_MAX, "two head_dim 128 dQ blocks per CU");
 
-inline long fb_lds_bytes(int T) {
-  return (long)(2 * fb_rows_q(T) + 2 * fb_rows_k(T)) * 32 * 2 + (long)2 * fb_rows_q(T) * 4;
+// every environment switch of the dispatch, read once at load
+const ap::AttnKnobs g_attn_knobs = ap::attn_knobs_from_env();
+
+// the plan of the last dtc_attn_fwd / dtc_attn_bwd that launched, written at the launch site (dtc_attn_last_launch)
+ap::AttnPlan g_attn_last{};
+
+// compute units of the current device, or 0 when the query fails (then no block order is balanced)
+int attn_cu_count() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 0;
+  return cus;
 }
 
-// LDS bytes of the resident kernels; 0 if the sequence does not fit (then the tiled kernels run)
-inline long res_lds_fwd(int T, int HD) { const long Tp = (T + 63) / 64 * 64; return Tp * (AttnLds<32>::KLD + HD + 16) * 2; }
-inline long res_lds_dkdv(int T, int HD) { const long Tp = (T + 63) / 64 * 64 + 64; return 2 * Tp * (HD + 16) * 2 + Tp * 8; }
-inline long res_lds_dq(int T, int HD) { const long Tp = (T + 63) / 64 * 64; return 2 * Tp * (HD + 16) * 2; }
-constexpr long LDS_MAX = 160 * 1024;
-
-bool use_resident(int T, int HD) {
-  static const int enabled = [] { const char* v = getenv("DTC_ATTN_RESIDENT"); return v ? atoi(v) : 1; }();
-  return enabled && HD == 32 && T % 4 == 0 && T <= RES_MAXT && res_lds_fwd(T, HD) <= LDS_MAX &&
-         res_lds_dkdv(T, HD) <= LDS_MAX && res_lds_dq(T, HD) <= LDS_MAX;
+// dynamic LDS bytes of the kernels sized by their layout structs (0: the plan already holds the size)
+int layout_lds_bytes(int kernel) {
+  switch (kernel) {
+    case ap::K_FWD32_128: return fw_lds_bytes<128>();
+    case ap::K_FWD32_64: case ap::K_FWD5_64_2: case ap::K_FWD5_64_3: return fw_lds_bytes<64>();
+    case ap::K_FWD_CHUNK_32: return ch_lds_fwd<32>();
+    case ap::K_FWD_CHUNK_64: return ch_lds_fwd<64>();
+    case ap::K_BWD_DQ_CHUNK_32: case ap::K_BWD_DKDV_CHUNK_32: return ch_lds_bwd<32>();
+    case ap::K_BWD_DQ_CHUNK_64: case ap::K_BWD_DKDV_CHUNK_64: return ch_lds_bwd<64>();
+    case ap::K_BWD_DQ32_64: case ap::K_BWD_DKDV32_64: case ap::K_BWD_MERGED32_64: return 2 * SW_STAGE * 2;
+    case ap::K_BWD_DQ32_128_DELTA_IN: case ap::K_BWD_DKDV32_128: return 2 * sw_stage<128>() * 2;
+    default: return 0;
+  }
+}
+ap::AttnPlan with_layout_lds(ap::AttnPlan p) {
+  for (int i = 0; i < p.nlaunch; ++i)
+    if (const int bytes = layout_lds_bytes(p.launch[i].kernel)) p.launch[i].lds = bytes;
+  return p;
+}
+ap::AttnPlan plan_fwd(int B, int T, int H, int HD, int flags, int cus) {
+  return with_layout_lds(ap::plan_attn_fwd(B, T, H, HD, flags, cus, g_attn_knobs));
+}
+ap::AttnPlan plan_bwd(int B, int T, int H, int HD, int flags, long ws_bytes, int cus) {
+  return with_layout_lds(ap::plan_attn_bwd(B, T, H, HD, flags, ws_bytes, cus, g_attn_knobs));
 }
 
-// chunked kernels for what the resident ones cannot hold (DTC_ATTN_CHUNK=0: the 256-thread tiled kernels)
-bool attn_chunk_enabled() {
-  static const int v = [] { const char* e = getenv("DTC_ATTN_CHUNK"); return e ? atoi(e) : 1; }();
-  return v != 0;
+// fw_order is a pure function of these four; the last one asked for is kept per host thread
+FwOrder cached_fw_order(int nqb, int nbh, int wps, int cus) {
+  thread_local int key[4] = {-1, -1, -1, -1};
+  thread_local FwOrder cached;
+  const int now[4] = {nqb, nbh, wps, cus};
+  if (!std::equal(key, key + 4, now)) {
+    cached = ap::fw_order(nqb, nbh, wps, cus);
+    std::copy(now, now + 4, key);
+  }
+  return cached;
 }
 
-template <typename K>
-void allow_lds(K kernel, long bytes) {  // > 64 KB of dynamic LDS must be opted into per kernel
-  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
+// > 64 KB of dynamic LDS must be opted into per kernel.  A host-only harness defines ATTN_ALLOW_LDS itself and
+// so compiles nothing that takes a kernel's address.
+#ifndef ATTN_ALLOW_LDS
+#define ATTN_ALLOW_LDS(kernel, bytes) \
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
+// Every kernel this file instantiates, one per ap::Kernel id.  Kernels are emitted into the code object in the
+// order they are first named, so naming them here keeps its layout independent of how the launch sites below
+// are arranged (the order is the one the code object has always had).
+[[maybe_unused]] const void* const ATTN_KERNELS[ap::K_COUNT - 1] = {
+    (const void*)attn_fwd_res_kernel<32>, (const void*)attn_fwd32_kernel<128>, (const void*)attn_fwd5_kernel<64, 2>,
+    (const void*)attn_fwd5_kernel<64, 3>, (const void*)attn_fwd32_kernel<64>, (const void*)attn_fwd_chunk_kernel<64>,
+    (const void*)attn_fwd_chunk_kernel<32>, (const void*)attn_fwd_kernel<32>, (const void*)attn_fwd_kernel<64>,
+    (const void*)attn_bwd_fused_kernel<32>, (const void*)attn_bwd_dkdv_res_kernel<32>,
+    (const void*)attn_bwd_dq_res_kernel<32>, (const void*)attn_bwd_res_kernel<32>,
+    (const void*)attn_bwd_dkdv32_kernel<128>, (const void*)attn_bwd_dq32_kernel<128, true>,
+    (const void*)attn_delta_kernel<128>, (const void*)attn_bwd_dq32_kernel<64>, (const void*)attn_bwd_dkdv32_kernel<64>,
+    (const void*)attn_bwd_merged32_kernel<64>, (const void*)attn_delta_kernel<64>,
+    (const void*)attn_bwd_dkdv_chunk_kernel<64>, (const void*)attn_bwd_dq_chunk_kernel<64>,
+    (const void*)attn_bwd_dkdv_chunk_kernel<32>, (const void*)attn_bwd_dq_chunk_kernel<32>,
+    (const void*)attn_delta_kernel<32>, (const void*)attn_bwd_dkdv_kernel<32>, (const void*)attn_bwd_dq_kernel<32>,
+    (const void*)attn_bwd_dkdv_kernel<64>, (const void*)attn_bwd_dq_kernel<64>};
+#endif
+// one planned launch `l` of `kernel` on the stream `st` of the enclosing entry point
+#define ATTN_LAUNCH(kernel, l, ...)                                                            \
+  do {                                                                                         \
+    if ((l).lds) ATTN_ALLOW_LDS(kernel, (l).lds);                                              \
+    hipLaunchKernelGGL(kernel, dim3((l).grid), dim3((l).block), (l).lds, st, __VA_ARGS__);     \
+  } while (0)
+
+template <int N>
+using hd_c = std::integral_constant<int, N>;
 
 }  // namespace
 
@@ -2176,205 +2231,130 @@ int dtc_attn_stamps(unsigned long long* host, long n) {
 #endif
 }
 
-// The CU-balanced order (FwOrder) for nqb query blocks x nbh (b, h) at WPS blocks per CU, or n = 0 when the
-// grid is not exactly one round of 8 equal XCDs.  Longest-processing-time-first per XCD: the query blocks,
-// heaviest first, each to the least-loaded CU with a free slot; CU c's s-th block becomes k = s * C + c.
-static FwOrder fw_order(int nqb, int nbh, int wps) {
-  static int cached_key = -1;
-  static FwOrder cached;
-  const int key = (nqb << 20) | (nbh << 4) | wps;
-  if (key == cached_key) return cached;
-  FwOrder ord{};
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 0;
-  const int C = cus / 8, per_xcd = nbh / 8 * nqb;
-  if (cus % 8 == 0 && nbh % 8 == 0 && C > 0 && per_xcd == C * wps && per_xcd <= FW_ORDER_MAX && nqb <= 255 &&
-      nbh / 8 <= 255) {
-    std::vector<int> load(C, 0), cnt(C, 0), used(nqb, 0);
-    for (int q = nqb - 1; q >= 0; --q)
-      for (int i = 0; i < nbh / 8; ++i) {
-        int c = -1;
-        for (int t = 0; t < C; ++t)
-          if (cnt[t] < wps && (c < 0 || load[t] < load[c])) c = t;
-        const int k = cnt[c] * C + c;
-        ord.q[k] = (unsigned char)q;
-        ord.j[k] = (unsigned char)used[q]++;
-        load[c] += q + 1;
-        ++cnt[c];
-      }
-    ord.n = per_xcd;
-  }
-  cached_key = key;
-  cached = ord;
-  return ord;
-}
-
-int dtc_attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, int HD, long flags, float scale,
+int dtc_attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, int head_dim, int flags, float scale,
                  hipStream_t st) {
-  if (use_resident(T, HD)) {
-    allow_lds(attn_fwd_res_kernel<32>, res_lds_fwd(T, HD));
-    // flags bit 0: plain wave -> query-group order (A/B of the SIMD-balanced order)
-    hipLaunchKernelGGL(attn_fwd_res_kernel<32>, dim3(B * H * 2), dim3(RES_THREADS), res_lds_fwd(T, HD), st, qkv, o,
-                       lse, B, T, H, scale, (int)!(flags & 1));
-    DTC_CHECK_LAUNCH();
-    return 0;
+  const int cus = attn_cu_count();
+  const ap::AttnPlan p = plan_fwd(B, T, H, head_dim, flags, cus);
+  if (p.err) return p.err;
+  const ap::Launch& l = p.launch[0];
+  auto chunk_or_tiled = [&](auto hd) {  // the two paths instantiated at head_dim 32 and 64
+    constexpr int HD = decltype(hd)::value;
+    if (p.path == ap::FWD_CHUNK) ATTN_LAUNCH(attn_fwd_chunk_kernel<HD>, l, qkv, o, lse, B, T, H, scale);
+    else ATTN_LAUNCH(attn_fwd_kernel<HD>, l, qkv, o, lse, B, T, H, scale);
+  };
+  switch (p.path) {
+    case ap::FWD_RESIDENT:
+      ATTN_LAUNCH(attn_fwd_res_kernel<32>, l, qkv, o, lse, B, T, H, scale, (int)!(flags & ap::FWD_PLAIN_WAVES));
+      break;
+    case ap::FWD_PIPE2:  // 2 waves per SIMD, heavy-first (n = 0)
+      ATTN_LAUNCH((attn_fwd5_kernel<64, 2>), l, qkv, o, lse, B, T, H, scale, FwOrder{});
+      break;
+    case ap::FWD_PIPE3:
+      // default at head_dim 64: the round-5 forward (2-deep K/V prefetch, V^T fragments ahead of the softmax, one
+      // code path per tile; 26.6-26.9 vs 28.2-28.5 us per layer, profiles/r5_attention.md) in the CU-balanced
+      // block order: 25.8 -> 24.2-24.5 us per GPT-2-small layer, bitwise identical (profiles/r6_attn_order_ab*.log)
+      ATTN_LAUNCH((attn_fwd5_kernel<64, 3>), l, qkv, o, lse, B, T, H, scale,
+                  p.order_n ? cached_fw_order(l.grid / (B * H), B * H, 3, cus) : FwOrder{});
+      break;
+    case ap::FWD_ROWS32:
+      // the 32-query-row kernel in the heavy-first block order (it takes no FwOrder, so there is no one-round
+      // precondition to meet): the one head_dim 128 forward, the round-4 A/B at head_dim 64
+      if (head_dim == 128) ATTN_LAUNCH(attn_fwd32_kernel<128>, l, qkv, o, lse, B, T, H, scale);
+      else ATTN_LAUNCH(attn_fwd32_kernel<64>, l, qkv, o, lse, B, T, H, scale);
+      break;
+    case ap::FWD_CHUNK:
+    case ap::FWD_TILED:
+      if (head_dim == 32) chunk_or_tiled(hd_c<32>{});
+      else chunk_or_tiled(hd_c<64>{});
+      break;
+    default: return 4004;  // a path this switch does not know: the plan and the launch sites disagree
   }
-  // head_dim 128: the 32-query-row kernel in the heavy-first block order (it takes no FwOrder, so there is
-  // no one-round precondition to meet); the A/B flags and DTC_ATTN_CHUNK pick head_dim 64 variants and are
-  // ignored here
-  if (HD == 128) {
-    allow_lds(attn_fwd32_kernel<128>, fw_lds_bytes<128>());
-    hipLaunchKernelGGL(attn_fwd32_kernel<128>, dim3(B * H * ((T + FW_QROWS - 1) / FW_QROWS)), dim3(FW_THREADS),
-                       fw_lds_bytes<128>(), st, qkv, o, lse, B, T, H, scale);
-    DTC_CHECK_LAUNCH();
-    return 0;
-  }
-  // default at head_dim 64: the round-5 forward (2-deep K/V prefetch, V^T fragments ahead of the softmax, one
-  // code path per tile; 26.6-26.9 vs 28.2-28.5 us per layer, profiles/r5_attention.md); flags bit 4 = the
-  // round-4 kernel (A/B),
-  // bit 2 = the 16-row chunked kernel
-  if (HD == 64 && (flags & 32) && !(flags & 16) && !(flags & 4) && attn_chunk_enabled()) {
-    allow_lds(attn_fwd5_kernel<64, 2>, fw_lds_bytes<64>());
-    FwOrder ord;
-    ord.n = 0;
-    hipLaunchKernelGGL((attn_fwd5_kernel<64, 2>), dim3(B * H * ((T + FW_QROWS - 1) / FW_QROWS)), dim3(FW_THREADS),
-                       fw_lds_bytes<64>(), st, qkv, o, lse, B, T, H, scale, ord);
-    DTC_CHECK_LAUNCH();
-    return 0;
-  }
-  if (HD == 64 && !(flags & 16) && !(flags & 4) && attn_chunk_enabled()) {
-    allow_lds(attn_fwd5_kernel<64, 3>, fw_lds_bytes<64>());
-    const int nqb = (T + FW_QROWS - 1) / FW_QROWS;
-    // CU-balanced block order (default; flags bit 6 = the heavy-first order, A/B): 25.8 -> 24.2-24.5 us per
-    // GPT-2-small layer, bitwise identical (profiles/r6_attn_order_ab*.log)
-    const FwOrder ord = (flags & 64) ? FwOrder{} : fw_order(nqb, B * H, 3);
-    hipLaunchKernelGGL((attn_fwd5_kernel<64, 3>), dim3(B * H * nqb), dim3(FW_THREADS), fw_lds_bytes<64>(), st, qkv, o,
-                       lse, B, T, H, scale, ord);
-    DTC_CHECK_LAUNCH();
-    return 0;
-  }
-  // flags bit 2: the 16-query-row chunked kernel instead of the 32-row one (A/B)
-  if (HD == 64 && !(flags & 4) && attn_chunk_enabled()) {
-    allow_lds(attn_fwd32_kernel<64>, fw_lds_bytes<64>());
-    hipLaunchKernelGGL(attn_fwd32_kernel<64>, dim3(B * H * ((T + FW_QROWS - 1) / FW_QROWS)), dim3(FW_THREADS),
-                       fw_lds_bytes<64>(), st, qkv, o, lse, B, T, H, scale);
-    DTC_CHECK_LAUNCH();
-    return 0;
-  }
-  if (attn_chunk_enabled() && (HD == 32 || HD == 64)) {
-    const dim3 g(B * H * ((T + CH_QROWS - 1) / CH_QROWS));
-    if (HD == 64) {
-      allow_lds(attn_fwd_chunk_kernel<64>, ch_lds_fwd<64>());
-      hipLaunchKernelGGL(attn_fwd_chunk_kernel<64>, g, dim3(CH_THREADS), ch_lds_fwd<64>(), st, qkv, o, lse, B, T, H, scale);
-    } else {
-      allow_lds(attn_fwd_chunk_kernel<32>, ch_lds_fwd<32>());
-      hipLaunchKernelGGL(attn_fwd_chunk_kernel<32>, g, dim3(CH_THREADS), ch_lds_fwd<32>(), st, qkv, o, lse, B, T, H, scale);
-    }
-    DTC_CHECK_LAUNCH();
-    return 0;
-  }
-  int nqb = (T + 63) / 64;
-  dim3 grid(B * H * nqb);
-  if (HD == 32) hipLaunchKernelGGL(attn_fwd_kernel<32>, grid, dim3(256), 0, st, qkv, o, lse, B, T, H, scale);
-  else if (HD == 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(256), 0, st, qkv, o, lse, B, T, H, scale);
-  else return 4001;
+  g_attn_last = p;
   DTC_CHECK_LAUNCH();
   return 0;
 }
 
-long dtc_attn_bwd_workspace_bytes(int B, int T, int H, int HD) { return (long)B * H * T * 4; }
+long dtc_attn_bwd_workspace_bytes(int B, int T, int H, int HD) {
+  (void)HD;
+  return ap::bwd_workspace_bytes(B, T, H);
+}
 
 int dtc_attn_bwd(const bf16* qkv, const bf16* o, const float* lse, const bf16* dout, bf16* dqkv, int flags, int B,
-                 int T, int H, int HD, float scale, float* ws, long ws_bytes, hipStream_t st) {
-  if (ws_bytes < dtc_attn_bwd_workspace_bytes(B, T, H, HD)) return 4002;
-  int nb = (T + 63) / 64;
-  dim3 grid(B * H * nb);
-  static const int merged = [] { const char* v = getenv("DTC_ATTN_MERGED"); return v ? atoi(v) : 1; }();
-  // DTC_ATTN_FUSED=0: the two-round merged/split resident kernels instead of the fused single round
-  static const int fused = [] { const char* v = getenv("DTC_ATTN_FUSED"); return v ? atoi(v) : 1; }();
-  // flags bit 0: force the two-round kernels (in-process A/B, benchmarks/attn_ab.py)
-  if (use_resident(T, HD) && fused && !(flags & 1) && fb_lds_bytes(T) <= LDS_MAX) {
-    allow_lds(attn_bwd_fused_kernel<32>, fb_lds_bytes(T));
-    hipLaunchKernelGGL(attn_bwd_fused_kernel<32>, dim3(B * H * 2), dim3(FB_THREADS), fb_lds_bytes(T), st, qkv, o, dout,
-                       lse, dqkv, B, T, H, scale);
-  } else if (use_resident(T, HD) && !merged) {
-    allow_lds(attn_bwd_dkdv_res_kernel<32>, res_lds_dkdv(T, HD));
-    allow_lds(attn_bwd_dq_res_kernel<32>, res_lds_dq(T, HD));
-    hipLaunchKernelGGL(attn_bwd_dkdv_res_kernel<32>, dim3(B * H * 2), dim3(RES_THREADS), res_lds_dkdv(T, HD), st, qkv,
-                       o, dout, lse, dqkv, B, T, H, scale);
-    hipLaunchKernelGGL(attn_bwd_dq_res_kernel<32>, dim3(B * H * 2), dim3(RES_THREADS), res_lds_dq(T, HD), st, qkv, o,
-                       dout, lse, dqkv, B, T, H, scale);
-  } else if (use_resident(T, HD)) {
-    const long lds_b = std::max(res_lds_dkdv(T, HD), res_lds_dq(T, HD));
-    allow_lds(attn_bwd_res_kernel<32>, lds_b);
-    hipLaunchKernelGGL(attn_bwd_res_kernel<32>, dim3(B * H * 4), dim3(RES_THREADS), lds_b, st, qkv, o, dout, lse,
-                       dqkv, B, T, H, scale);
-  } else if (HD == 128) {
-    // head_dim 128: delta pass, then the 32x32x16 dK/dV (1 wave per SIMD) and dQ (2 per SIMD) kernels as two
-    // launches (their register budgets differ, so they do not share the merged kernel); flags ignored
-    constexpr int lb = 2 * sw_stage<128>() * 2;
-    static_assert(2 * lb <= LDS_MAX, "two dQ blocks per CU");
-    allow_lds(attn_bwd_dkdv32_kernel<128>, lb);
-    allow_lds((attn_bwd_dq32_kernel<128, true>), lb);
-    const dim3 g32(B * H * ((T + FW_QROWS - 1) / FW_QROWS));
-    launch_attn_delta<128>(o, dout, ws, B, T, H, st);
-    hipLaunchKernelGGL(attn_bwd_dkdv32_kernel<128>, g32, dim3(FW_THREADS), lb, st, qkv, dout, lse, ws, dqkv, B, T, H,
-                       scale);
-    hipLaunchKernelGGL((attn_bwd_dq32_kernel<128, true>), g32, dim3(FW_THREADS), lb, st, qkv, o, dout, lse, ws, dqkv,
-                       B, T, H, scale);
-  } else if (attn_chunk_enabled() && (HD == 32 || HD == 64)) {
-    const dim3 g(B * H * ((T + CH_QROWS - 1) / CH_QROWS)), gk(B * H * ((T + CHB_KROWS - 1) / CHB_KROWS));
-    if (HD == 64 && !(flags & 4)) {
-      // 32x32x16 kernels (flags bit 2: the 16-row chunked ones); dQ first: it writes delta
-      constexpr int lb = 2 * SW_STAGE * 2;
-      allow_lds(attn_bwd_dq32_kernel<64>, lb);
-      allow_lds(attn_bwd_dkdv32_kernel<64>, lb);
-      const dim3 g32(B * H * ((T + FW_QROWS - 1) / FW_QROWS));
-      // DTC_ATTN_BWD_MERGED (default 1; flags bit 3 forces it): delta pass + one launch of dK/dV and dQ
-      // blocks -- 82.9 vs 85.3 us per layer, step 11.35-11.37 vs 11.40-11.42 ms (profiles/r4_attn_merged.log)
-      static const int bwd_merged = [] { const char* v = getenv("DTC_ATTN_BWD_MERGED"); return v ? atoi(v) : 1; }();
-      if (bwd_merged || (flags & 8)) {
-        allow_lds(attn_bwd_merged32_kernel<64>, lb);
-        launch_attn_delta<64>(o, dout, ws, B, T, H, st);
-        hipLaunchKernelGGL(attn_bwd_merged32_kernel<64>, dim3(2 * g32.x), dim3(FW_THREADS), lb, st, qkv, dout, lse, ws,
-                           dqkv, B, T, H, scale, (int)g32.x);
-      } else {
-        hipLaunchKernelGGL(attn_bwd_dq32_kernel<64>, g32, dim3(FW_THREADS), lb, st, qkv, o, dout, lse, ws, dqkv, B, T,
-                           H, scale);
-        hipLaunchKernelGGL(attn_bwd_dkdv32_kernel<64>, g32, dim3(FW_THREADS), lb, st, qkv, dout, lse, ws, dqkv, B, T,
-                           H, scale);
-      }
-    } else if (HD == 64) {
-      allow_lds(attn_bwd_dkdv_chunk_kernel<64>, ch_lds_bwd<64>());
-      allow_lds(attn_bwd_dq_chunk_kernel<64>, ch_lds_bwd<64>());
-      // dQ first: it writes delta (ws) for the dK/dV kernel
-      hipLaunchKernelGGL(attn_bwd_dq_chunk_kernel<64>, g, dim3(CH_THREADS), ch_lds_bwd<64>(), st, qkv, o, dout, lse,
-                         ws, dqkv, B, T, H, scale);
-      hipLaunchKernelGGL(attn_bwd_dkdv_chunk_kernel<64>, gk, dim3(CHB_THREADS), ch_lds_bwd<64>(), st, qkv, dout, lse, ws,
-                         dqkv, B, T, H, scale);
+                 int T, int H, int head_dim, float scale, float* ws, long ws_bytes, hipStream_t st) {
+  const ap::AttnPlan p = plan_bwd(B, T, H, head_dim, flags, ws_bytes, attn_cu_count());
+  if (p.err) return p.err;
+  const ap::Launch* l = p.launch;
+  auto chunk_or_tiled = [&](auto hd) {  // the two paths instantiated at head_dim 32 and 64
+    constexpr int HD = decltype(hd)::value;
+    if (p.path == ap::BWD_CHUNK) {  // dQ first: it writes delta (ws) for the dK/dV kernel
+      ATTN_LAUNCH(attn_bwd_dq_chunk_kernel<HD>, l[0], qkv, o, dout, lse, ws, dqkv, B, T, H, scale);
+      ATTN_LAUNCH(attn_bwd_dkdv_chunk_kernel<HD>, l[1], qkv, dout, lse, ws, dqkv, B, T, H, scale);
     } else {
-      allow_lds(attn_bwd_dkdv_chunk_kernel<32>, ch_lds_bwd<32>());
-      allow_lds(attn_bwd_dq_chunk_kernel<32>, ch_lds_bwd<32>());
-      // dQ first: it writes delta (ws) for the dK/dV kernel
-      hipLaunchKernelGGL(attn_bwd_dq_chunk_kernel<32>, g, dim3(CH_THREADS), ch_lds_bwd<32>(), st, qkv, o, dout, lse,
-                         ws, dqkv, B, T, H, scale);
-      hipLaunchKernelGGL(attn_bwd_dkdv_chunk_kernel<32>, gk, dim3(CHB_THREADS), ch_lds_bwd<32>(), st, qkv, dout, lse, ws,
-                         dqkv, B, T, H, scale);
+      ATTN_LAUNCH(attn_delta_kernel<HD>, l[0], o, dout, ws, B, T, H);
+      ATTN_LAUNCH(attn_bwd_dkdv_kernel<HD>, l[1], qkv, dout, lse, ws, dqkv, B, T, H, scale);
+      ATTN_LAUNCH(attn_bwd_dq_kernel<HD>, l[2], qkv, dout, lse, ws, dqkv, B, T, H, scale);
     }
-  } else if (HD == 32) {
-    launch_attn_delta<32>(o, dout, ws, B, T, H, st);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<32>, grid, dim3(256), 0, st, qkv, dout, lse, ws, dqkv, B, T, H, scale);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<32>, grid, dim3(256), 0, st, qkv, dout, lse, ws, dqkv, B, T, H, scale);
-  } else if (HD == 64) {
-    launch_attn_delta<64>(o, dout, ws, B, T, H, st);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<64>, grid, dim3(256), 0, st, qkv, dout, lse, ws, dqkv, B, T, H, scale);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<64>, grid, dim3(256), 0, st, qkv, dout, lse, ws, dqkv, B, T, H, scale);
-  } else {
-    return 4001;
+  };
+  switch (p.path) {
+    case ap::BWD_RES_FUSED:
+      ATTN_LAUNCH(attn_bwd_fused_kernel<32>, l[0], qkv, o, dout, lse, dqkv, B, T, H, scale);
+      break;
+    case ap::BWD_RES_SPLIT:
+      ATTN_LAUNCH(attn_bwd_dkdv_res_kernel<32>, l[0], qkv, o, dout, lse, dqkv, B, T, H, scale);
+      ATTN_LAUNCH(attn_bwd_dq_res_kernel<32>, l[1], qkv, o, dout, lse, dqkv, B, T, H, scale);
+      break;
+    case ap::BWD_RES_MERGED:
+      ATTN_LAUNCH(attn_bwd_res_kernel<32>, l[0], qkv, o, dout, lse, dqkv, B, T, H, scale);
+      break;
+    case ap::BWD_ROWS32_128:
+      // delta pass, then the 32x32x16 dK/dV (1 wave per SIMD) and dQ (2 per SIMD) kernels as two launches (their
+      // register budgets differ, so they do not share the merged kernel)
+      ATTN_LAUNCH(attn_delta_kernel<128>, l[0], o, dout, ws, B, T, H);
+      ATTN_LAUNCH(attn_bwd_dkdv32_kernel<128>, l[1], qkv, dout, lse, ws, dqkv, B, T, H, scale);
+      ATTN_LAUNCH((attn_bwd_dq32_kernel<128, true>), l[2], qkv, o, dout, lse, ws, dqkv, B, T, H, scale);
+      break;
+    case ap::BWD_ROWS32_MERGED:
+      // delta pass + one launch of dK/dV and dQ blocks -- 82.9 vs 85.3 us per layer, step 11.35-11.37 vs
+      // 11.40-11.42 ms (profiles/r4_attn_merged.log)
+      ATTN_LAUNCH(attn_delta_kernel<64>, l[0], o, dout, ws, B, T, H);
+      ATTN_LAUNCH(attn_bwd_merged32_kernel<64>, l[1], qkv, dout, lse, ws, dqkv, B, T, H, scale, l[1].grid / 2);
+      break;
+    case ap::BWD_ROWS32_SPLIT:  // dQ first: it writes delta
+      ATTN_LAUNCH(attn_bwd_dq32_kernel<64>, l[0], qkv, o, dout, lse, ws, dqkv, B, T, H, scale);
+      ATTN_LAUNCH(attn_bwd_dkdv32_kernel<64>, l[1], qkv, dout, lse, ws, dqkv, B, T, H, scale);
+      break;
+    case ap::BWD_CHUNK:
+    case ap::BWD_TILED:
+      if (head_dim == 32) chunk_or_tiled(hd_c<32>{});
+      else chunk_or_tiled(hd_c<64>{});
+      break;
+    default: return 4004;  // a path this switch does not know: the plan and the launch sites disagree
   }
+  g_attn_last = p;
   DTC_CHECK_LAUNCH();
   return 0;
 }
 
+// What the matching call would return and record, without launching: dir 1 = dtc_attn_fwd (ws_bytes unused),
+// 2 = dtc_attn_bwd.  out as dtc_attn_last_launch's; zeros when the call would refuse.
+int dtc_attn_plan(int dir, int B, int T, int H, int HD, int flags, long ws_bytes, int* out) {
+  const int cus = attn_cu_count();
+  const ap::AttnPlan p = dir == ap::DIR_BWD ? plan_bwd(B, T, H, HD, flags, ws_bytes, cus) : plan_fwd(B, T, H, HD, flags, cus);
+  ap::to_record(p, out);
+  return p.err;
+}
+
+// the record of the last attention call that launched (ap::to_record): out[17] = direction (1 forward, 2
+// backward), path, block order asked for, its n, launch count, then kernel id, grid, block and dynamic LDS bytes
+// of up to three launches
+int dtc_attn_last_launch(int* out) {
+  ap::to_record(g_attn_last, out);
+  return 0;
+}
+// sizes of the record and of the enums that ops/attention.py mirrors as name tables
+int dtc_attn_rec_ints() { return ap::REC_INTS; }
+int dtc_attn_kernel_count() { return ap::K_COUNT; }
+int dtc_attn_path_count() { return ap::PATH_COUNT; }
+
 }  // extern "C"
+

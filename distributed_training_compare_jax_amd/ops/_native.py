@@ -165,9 +165,14 @@ def _declare(lib):
         "dtc_embed_sort": ([vp, i, i, vp, vp], i),
         "dtc_embed_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, f, l, vp, l, i, vp, vp, i, vp], i),
         "dtc_embed_sq_slots": ([i, i, i], l),
-        "dtc_attn_fwd": ([vp, vp, vp, i, i, i, i, l, f, vp], i),
+        "dtc_attn_fwd": ([vp, vp, vp, i, i, i, i, i, f, vp], i),
         "dtc_attn_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, l, vp], i),
         "dtc_attn_bwd_workspace_bytes": ([i, i, i, i], l),
+        "dtc_attn_plan": ([i, i, i, i, i, i, l, ctypes.POINTER(c_int)], i),
+        "dtc_attn_last_launch": ([ctypes.POINTER(c_int)], i),
+        "dtc_attn_rec_ints": ([], i),
+        "dtc_attn_kernel_count": ([], i),
+        "dtc_attn_path_count": ([], i),
         "dtc_ce_combine": ([vp, i, i, l, l, vp, vp, vp, f, vp, i, vp], i),
         "dtc_ce_eval_finish": ([vp, l, l, vp, i, l, l, i, i, i, vp, vp, vp, vp, vp, vp], i),
         "dtc_row_argmax_f32": ([vp, l, i, i, vp, vp, vp], i),

@@ -13,10 +13,19 @@ fp32 tensors (the exact-fp32 parity mode) run ``csrc/attention_f32.hip``: the sa
 
 Layout: the fused QKV GEMM writes ``qkv[B, T, 3, H, hd]`` (bf16); attention reads Q/K/V
 in place with strides and writes ``o[B, T, H, hd]`` which is directly the out_proj input.
+
+Which bf16 kernels a call runs is decided in one place, ``csrc/attn_plan.h``: ``plan_attn_fwd`` / ``plan_attn_bwd``
+map (B, T, H, head_dim, flags, CU count, the ``DTC_ATTN_*`` knobs) to a path, its launches (kernel, grid, block,
+LDS bytes) and the block order, and ``dtc_attn_fwd`` / ``dtc_attn_bwd`` launch from that plan.  :func:`plan_fwd` /
+:func:`plan_bwd` ask the same plan without launching, and :func:`last_launch` reads the record the launch site
+wrote, so a test can assert which kernels a shape reached.  :class:`FwdFlags` / :class:`BwdFlags` name the A/B bits.
 """
 
 from __future__ import annotations
 
+import collections
+import ctypes
+import enum
 
 import torch
 
@@ -24,13 +33,105 @@ from . import _native as N
 from .gemm import _workspace
 
 
+class FwdFlags(enum.IntFlag):
+    """A/B switches of one :func:`attn_fwd` call (``ap::FwdFlags`` in ``csrc/attn_plan.h``)."""
+    PLAIN_WAVES = 1    # resident kernel (head_dim 32): plain wave → query-group order
+    CHUNK16 = 4        # head_dim 64: the 16-row chunk kernel
+    ROUND4 = 16        # head_dim 64: the round-4 32-row kernel
+    WPS2 = 32          # head_dim 64: the round-5 pipeline at 2 waves per SIMD (the default runs it at 3)
+    HEAVY_FIRST = 64   # head_dim 64: the round-5 pipeline in heavy-first block order, not CU-balanced
+
+
+class BwdFlags(enum.IntFlag):
+    """A/B switches of one :func:`attn_bwd` call (``ap::BwdFlags`` in ``csrc/attn_plan.h``)."""
+    TWO_ROUND = 1      # resident kernels (head_dim 32): the two-round kernels, not the fused single round
+    CHUNK16 = 4        # head_dim 64: the 16-row chunk kernels
+    FORCE_MERGED = 8   # head_dim 64: the merged dK/dV + dQ launch even with DTC_ATTN_BWD_MERGED=0
+
+
+# enums of csrc/attn_plan.h as names, in its order (last_launch checks the counts once; tests/test_attn_plan_cpu.py
+# holds the kernel names to the header's own table)
+DIRECTIONS = ("none", "fwd", "bwd")
+ORDERS = ("none", "heavy_first", "balanced")
+PATHS = ("none", "fwd_resident", "fwd_pipe3", "fwd_pipe2", "fwd_rows32", "fwd_chunk", "fwd_tiled", "bwd_res_fused",
+         "bwd_res_split", "bwd_res_merged", "bwd_rows32_128", "bwd_rows32_merged", "bwd_rows32_split", "bwd_chunk",
+         "bwd_tiled")
+KERNELS = ("none", "attn_delta_kernel<32>", "attn_delta_kernel<64>", "attn_delta_kernel<128>", "attn_fwd_kernel<32>",
+           "attn_fwd_kernel<64>", "attn_fwd_res_kernel<32>", "attn_fwd_chunk_kernel<32>", "attn_fwd_chunk_kernel<64>",
+           "attn_fwd32_kernel<64>", "attn_fwd32_kernel<128>", "attn_fwd5_kernel<64,2>", "attn_fwd5_kernel<64,3>",
+           "attn_bwd_dkdv_kernel<32>", "attn_bwd_dkdv_kernel<64>", "attn_bwd_dq_kernel<32>", "attn_bwd_dq_kernel<64>",
+           "attn_bwd_fused_kernel<32>", "attn_bwd_dkdv_res_kernel<32>", "attn_bwd_dq_res_kernel<32>",
+           "attn_bwd_res_kernel<32>", "attn_bwd_dq_chunk_kernel<32>", "attn_bwd_dq_chunk_kernel<64>",
+           "attn_bwd_dkdv_chunk_kernel<32>", "attn_bwd_dkdv_chunk_kernel<64>", "attn_bwd_dq32_kernel<64>",
+           "attn_bwd_dq32_kernel<128,true>", "attn_bwd_dkdv32_kernel<64>", "attn_bwd_dkdv32_kernel<128>",
+           "attn_bwd_merged32_kernel<64>")
+REC_INTS = 17
+_ENUMS_CHECKED = [False]
+
+Launch = collections.namedtuple("Launch", "kernel grid block lds")
+
+
+class AttnLaunch(collections.namedtuple("AttnLaunch", "direction path order order_n launches")):
+    """``direction`` fwd / bwd, ``path`` (one of :data:`PATHS`), the block ``order`` asked of ``attn_fwd5<64,3>``
+    (one of :data:`ORDERS`; ``order_n`` = blocks per XCD of the balanced order, 0 when the grid is not one round
+    and the kernel runs heavy-first after all) and the ``launches`` in order, each a :class:`Launch` with the
+    kernel's name (one of :data:`KERNELS`), grid, block and dynamic LDS bytes."""
+    __slots__ = ()
+
+    @property
+    def kernels(self):
+        return tuple(l.kernel for l in self.launches)
+
+
+def _record(out) -> AttnLaunch:
+    v = list(out)
+    launches = tuple(Launch(KERNELS[v[5 + 4 * i]], *v[6 + 4 * i:9 + 4 * i]) for i in range(v[4]))
+    return AttnLaunch(DIRECTIONS[v[0]], PATHS[v[1]], ORDERS[v[2]], v[3], launches)
+
+
+def _rec_buffer():
+    if not _ENUMS_CHECKED[0]:
+        L = N.lib()
+        assert (L.dtc_attn_kernel_count(), L.dtc_attn_path_count(), L.dtc_attn_rec_ints()) == (
+            len(KERNELS), len(PATHS), REC_INTS)
+        _ENUMS_CHECKED[0] = True
+    return (ctypes.c_int * REC_INTS)()
+
+
+def last_launch() -> AttnLaunch:
+    """What the last bf16 :func:`attn_fwd` / :func:`attn_bwd` of this process launched, as recorded at the launch
+    site from its plan.  Tests assert it; nothing on the hot path reads it."""
+    out = _rec_buffer()
+    N.check(N.lib().dtc_attn_last_launch(out), "dtc_attn_last_launch")
+    return _record(out)
+
+
+def plan_fwd(B: int, T: int, H: int, hd: int, flags: int = 0) -> AttnLaunch:
+    """The record a bf16 ``attn_fwd`` of this shape and ``flags`` would leave, without launching anything.  A
+    shape the call would refuse raises as the call does."""
+    out = _rec_buffer()
+    N.check(N.lib().dtc_attn_plan(1, B, T, H, hd, int(flags), 0, out), "dtc_attn_plan")
+    return _record(out)
+
+
+def plan_bwd(B: int, T: int, H: int, hd: int, flags: int = 0, ws_bytes: int | None = None) -> AttnLaunch:
+    """As :func:`plan_fwd`, for ``attn_bwd`` (``ws_bytes``: the workspace the call would hold; default: what it
+    needs)."""
+    L = N.lib()
+    ws_bytes = int(L.dtc_attn_bwd_workspace_bytes(B, T, H, hd)) if ws_bytes is None else ws_bytes
+    out = _rec_buffer()
+    N.check(L.dtc_attn_plan(2, B, T, H, hd, int(flags), ws_bytes, out), "dtc_attn_plan")
+    return _record(out)
+
+
 def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags: int = 0):
-    """qkv [B,T,3*H*hd] → (o [B,T,H*hd], lse [B,H,T] fp32, natural-log units).  ``flags`` (A/B switches of
-    ``dtc_attn_fwd``): bit 0 the resident kernel's plain wave → query-group order; bit 2 the 16-row chunked
-    kernel; bit 4 the round-4 32-row kernel; bit 5 the round-5 forward at 2 waves per SIMD (the default
-    runs it at 3); bit 6 its heavy-first block order (the default assigns query blocks to CU slots
-    longest-processing-time-first).  Every bit picks a head_dim 64 (bit 0: head_dim 32) variant; head_dim 128
-    has one forward kernel and ignores ``flags``."""
+    """qkv [B,T,3*H*hd] → (o [B,T,H*hd], lse [B,H,T] fp32, natural-log units).  ``flags``: a :class:`FwdFlags`
+    (or its integer), A/B switches of the bf16 kernels.  At head_dim 32 only ``PLAIN_WAVES`` means anything, and
+    only on the resident kernel.  At head_dim 64 the default is the round-5 pipeline at 3 waves per SIMD with
+    query blocks assigned to CU slots longest-processing-time-first; ``HEAVY_FIRST`` keeps that kernel in
+    heavy-first order, ``WPS2`` runs it at 2 waves per SIMD, ``ROUND4`` picks the round-4 32-row kernel and
+    ``CHUNK16`` the 16-row chunk kernel (``CHUNK16`` beats ``ROUND4`` beats ``WPS2``).  head_dim 128 has one
+    forward kernel and ignores ``flags``."""
     B, T, C3 = qkv.shape
     hd = C3 // (3 * n_heads)
     scale = scale if scale is not None else hd ** -0.5
@@ -59,9 +160,11 @@ def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags:
 
 def attn_bwd(qkv: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor, n_heads: int,
              scale: float | None = None, flags: int = 0) -> torch.Tensor:
-    """Returns dqkv [B,T,3*H*hd] (same dtype as qkv).  ``flags`` bit 0 forces the two-round resident
-    kernels instead of the fused single-round one (A/B and tests).  head_dim 128 has one backward path
-    (delta pass, dK/dV kernel, dQ kernel) and ignores ``flags``."""
+    """Returns dqkv [B,T,3*H*hd] (same dtype as qkv).  ``flags``: a :class:`BwdFlags` (or its integer), A/B
+    switches of the bf16 kernels.  ``TWO_ROUND`` forces the two-round resident kernels instead of the fused
+    single-round one (head_dim 32, resident shapes only); at head_dim 64 ``CHUNK16`` picks the 16-row chunk pair
+    and ``FORCE_MERGED`` the delta pass + merged launch even with ``DTC_ATTN_BWD_MERGED=0`` (``CHUNK16`` wins).
+    head_dim 128 has one backward path (delta pass, dK/dV kernel, dQ kernel) and ignores ``flags``."""
     B, T, C3 = qkv.shape
     hd = C3 // (3 * n_heads)
     scale = scale if scale is not None else hd ** -0.5

@@ -44,6 +44,9 @@ SHAPES = [(1, 72, 1, 128), (2, 200, 2, 128), (1, 777, 3, 128), (1, 1024, 2, 128)
 CASES = [pytest.param(s, False, id="x".join(map(str, s))) for s in SHAPES] + [
     pytest.param(SHAPES[3], True, id="1x1024x2x128-spike")]
 FWD, BWD = "attn_fwd32<128>", "attn_bwd_{dkdv32,dq32}<128>"
+# what A.last_launch() must name after a head_dim 128 call, whatever the flags
+FWD_KERNELS = ("attn_fwd32_kernel<128>",)
+BWD_KERNELS = ("attn_delta_kernel<128>", "attn_bwd_dkdv32_kernel<128>", "attn_bwd_dq32_kernel<128,true>")
 
 
 @pytest.mark.parametrize("shape,spike", CASES)
@@ -52,6 +55,7 @@ def test_hd128_fwd_blocks(cuda, shape, spike):
     B, T, H, hd = shape
     qkv, _, ref, floor = _attn_case(B, T, H, hd, spike)
     o, lse = A.attn_fwd(qkv.to(cuda), H)
+    assert A.last_launch().kernels == FWD_KERNELS, A.last_launch()
     assert o.dtype == torch.bfloat16 and lse.dtype == torch.float32 and lse.shape == (B, H, T)
     o = o.view(B, T, H, hd)
     _report(FWD, shape, spike, "o", o, ref, floor)
@@ -70,6 +74,7 @@ def test_hd128_bwd_blocks(cuda, shape, spike):
     qkv_d, do_d = qkv.to(cuda), do.to(cuda)
     o, lse = A.attn_fwd(qkv_d, H)
     d = A.attn_bwd(qkv_d, o, lse, do_d, H).view(B, T, 3, H, hd)
+    assert A.last_launch().kernels == BWD_KERNELS, A.last_launch()
     outs = {n: d[:, :, "qkv".index(n[1])] for n in ("dq", "dk", "dv")}
     for n, t in outs.items():
         _report(BWD, shape, spike, n, t, ref, floor)
@@ -121,6 +126,15 @@ def test_hd128_deterministic(cuda, dtype):
     d2 = A.attn_bwd(qkv, o1, l1, do, H)
     assert torch.equal(d1, d2)
     assert bool(torch.isfinite(d1.float()).all())
+    if dtype == torch.bfloat16:  # head_dim 128 ignores every flag: same record, same bits
+        bwd = A.last_launch()
+        assert torch.equal(d1, A.attn_bwd(qkv, o1, l1, do, H, flags=15)) and A.last_launch() == bwd
+        assert bwd.kernels == BWD_KERNELS, bwd
+        o3, l3 = A.attn_fwd(qkv, H)
+        fwd = A.last_launch()
+        o4, l4 = A.attn_fwd(qkv, H, flags=127)
+        assert A.last_launch() == fwd and fwd.kernels == FWD_KERNELS, (fwd, A.last_launch())
+        assert torch.equal(o3, o4) and torch.equal(l3, l4) and torch.equal(o3, o1)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])

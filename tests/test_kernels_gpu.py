@@ -258,10 +258,19 @@ def test_attention(cuda, B, T, H, hd):
     qkv = _r(B, T, 3 * H * hd, seed=20)
     do = _r(B, T, H * hd, seed=21)
     oc, lsec, dref = _attn_ref64(qkv, do, H)  # float64, independent of the GPU's o and lse
+    # the path each shape must take: resident at head_dim 32 while T <= 512 and T % 4 == 0 (200 included), the
+    # chunk kernels beyond (520, 700); the round-5 pipeline and the delta pass + merged backward at head_dim 64
+    resident = hd == 32 and T <= 512
+    fwd = "attn_fwd5_kernel<64,3>" if hd == 64 else "attn_fwd_res_kernel<32>" if resident else "attn_fwd_chunk_kernel<32>"
+    bwd = (("attn_delta_kernel<64>", "attn_bwd_merged32_kernel<64>") if hd == 64 else
+           ("attn_bwd_fused_kernel<32>",) if resident else
+           ("attn_bwd_dq_chunk_kernel<32>", "attn_bwd_dkdv_chunk_kernel<32>"))
     o, lse = A.attn_fwd(qkv, H)
+    assert A.last_launch().kernels == (fwd,), A.last_launch()
     _close(o.cpu(), oc, 2e-2, "attn_o")
     _close(lse.cpu(), lsec, 1e-3, "attn_lse")
     dqkv = A.attn_bwd(qkv, o, lse, do, H)
+    assert A.last_launch().kernels == bwd, A.last_launch()
     d3, r3 = dqkv.cpu().float().view(B, T, 3, -1), dref.view(B, T, 3, -1)
     for i, n in enumerate("qkv"):
         _close(d3[:, :, i], r3[:, :, i], 3e-2, f"attn_d{n}")
@@ -271,7 +280,7 @@ def test_attention(cuda, B, T, H, hd):
 @pytest.mark.parametrize("B,T,H", [(2, 1024, 3), (1, 777, 2)])
 def test_attention_fwd32_vs_chunk_and_reference(cuda, B, T, H, spike):
     """head_dim 64 forward on the 32-query-per-wave 32x32x16 kernel (default) against the 16-row chunked
-    kernel (flags bit 2) and the fp32 reference.  ``spike``: one key scaled up mid-sequence so the
+    kernel (``CHUNK16``) and the fp32 reference.  ``spike``: one key scaled up mid-sequence so the
     running max jumps by far more than the deferred-max threshold (2^8) at a late tile -- the rescale
     branch runs on most rows (cdna_hip_programming.md §5.4 rule 26)."""
     hd = 64
@@ -280,20 +289,28 @@ def test_attention_fwd32_vs_chunk_and_reference(cuda, B, T, H, spike):
         v = qkv.view(B, T, 3, H, hd)
         v[:, T // 2 + 5, 1] *= 12.0  # key row T/2+5 of every head: its scores dominate later queries
     o, lse = A.attn_fwd(qkv, H)
-    o4, lse4 = A.attn_fwd(qkv, H, flags=4)
+    assert A.last_launch().kernels == ("attn_fwd5_kernel<64,3>",), A.last_launch()
+    o4, lse4 = A.attn_fwd(qkv, H, flags=A.FwdFlags.CHUNK16)
+    assert A.last_launch().kernels == ("attn_fwd_chunk_kernel<64>",), A.last_launch()
     oc, lsec = A.attn_fwd(qkv.cpu().float(), H)
     _close(o.cpu(), oc, 2e-2, "attn32_o")
     _close(lse.cpu(), lsec, 1e-3, "attn32_lse")
     _close(o.float(), o4.float(), 2e-2, "attn32_vs_chunk")
-    o4r, lse4r = A.attn_fwd(qkv, H, flags=16)  # the round-4 32-row kernel (the default is the round-5 pipeline)
+    o4r, lse4r = A.attn_fwd(qkv, H, flags=A.FwdFlags.ROUND4)  # the round-4 32-row kernel (default: the round-5 pipeline)
+    assert A.last_launch().kernels == ("attn_fwd32_kernel<64>",), A.last_launch()
     _close(o4r.cpu(), oc, 2e-2, "attn32r4_o")
     _close(lse4r.cpu(), lsec, 1e-3, "attn32r4_lse")
     assert torch.equal(o, A.attn_fwd(qkv, H)[0])  # deterministic
     # backward: the 32x32x16 dQ and dK/dV kernels (default) vs the 16-row chunked ones vs fp32
     do = _r(B, T, H * hd, seed=41)
+    merged = ("attn_delta_kernel<64>", "attn_bwd_merged32_kernel<64>")
     d = A.attn_bwd(qkv, o, lse, do, H)
-    d4 = A.attn_bwd(qkv, o, lse, do, H, flags=4)
-    d8 = A.attn_bwd(qkv, o, lse, do, H, flags=8)  # merged: delta pass + dK/dV and dQ blocks in one launch
+    assert A.last_launch().kernels == merged, A.last_launch()
+    d4 = A.attn_bwd(qkv, o, lse, do, H, flags=A.BwdFlags.CHUNK16)
+    assert A.last_launch().kernels == ("attn_bwd_dq_chunk_kernel<64>", "attn_bwd_dkdv_chunk_kernel<64>"), A.last_launch()
+    # merged: delta pass + dK/dV and dQ blocks in one launch
+    d8 = A.attn_bwd(qkv, o, lse, do, H, flags=A.BwdFlags.FORCE_MERGED)
+    assert A.last_launch().kernels == merged, A.last_launch()
     dref = A.attn_bwd(qkv.cpu().float(), o.cpu().float(), lse.cpu(), do.cpu().float(), H)
     d3, r3, o3 = d.cpu().float().view(B, T, 3, -1), dref.view(B, T, 3, -1), d4.cpu().float().view(B, T, 3, -1)
     m3 = d8.cpu().float().view(B, T, 3, -1)
@@ -302,18 +319,26 @@ def test_attention_fwd32_vs_chunk_and_reference(cuda, B, T, H, spike):
         _close(d3[:, :, i], o3[:, :, i], 3e-2, f"attn32_vs_chunk_d{n}")
         _close(m3[:, :, i], r3[:, :, i], 3e-2, f"attn32_merged_d{n}")
     assert torch.equal(d, A.attn_bwd(qkv, o, lse, do, H))  # deterministic
-    assert torch.equal(d8, A.attn_bwd(qkv, o, lse, do, H, flags=8))
+    assert torch.equal(d8, A.attn_bwd(qkv, o, lse, do, H, flags=A.BwdFlags.FORCE_MERGED))
 
 
 def test_attention_fwd_balanced_order_bitwise(cuda):
     """GPT-2 small shape (B8 T1024 H12: 768 blocks = one round at 3 per CU): the CU-balanced block order
-    (default) computes every (query block, b, h) exactly once, bitwise equal to the heavy-first order (flags
-    bit 6) and to the 2-waves-per-SIMD form (bit 5, heavy-first)."""
+    (default) computes every (query block, b, h) exactly once, bitwise equal to the heavy-first order
+    (``HEAVY_FIRST``) and to the 2-waves-per-SIMD form (``WPS2``, heavy-first).  The record must say that the
+    balanced order was really taken: fw_order falls back to heavy-first, n = 0, on any grid that is not one round."""
     B, T, H, hd = 8, 1024, 12, 64
     qkv = _r(B, T, 3 * H * hd, seed=44)
+    # 768 blocks on 256 CUs at 3 per CU: one round, so the balanced order is taken, 96 blocks per XCD
     o, lse = A.attn_fwd(qkv, H)
-    o6, lse6 = A.attn_fwd(qkv, H, flags=64)
-    o5, lse5 = A.attn_fwd(qkv, H, flags=32)
+    rec = A.last_launch()
+    assert (rec.kernels, rec.order, rec.order_n) == (("attn_fwd5_kernel<64,3>",), "balanced", 96), rec
+    o6, lse6 = A.attn_fwd(qkv, H, flags=A.FwdFlags.HEAVY_FIRST)
+    rec = A.last_launch()
+    assert (rec.kernels, rec.order, rec.order_n) == (("attn_fwd5_kernel<64,3>",), "heavy_first", 0), rec
+    o5, lse5 = A.attn_fwd(qkv, H, flags=A.FwdFlags.WPS2)
+    rec = A.last_launch()
+    assert (rec.kernels, rec.order, rec.order_n) == (("attn_fwd5_kernel<64,2>",), "none", 0), rec
     assert torch.equal(o, o6) and torch.equal(lse, lse6)
     assert torch.equal(o, o5) and torch.equal(lse, lse5)
     # one head of one sequence against the fp32 reference (the order only moves whole blocks)
@@ -331,12 +356,33 @@ def test_attention_bwd_fused_matches_two_round(cuda, B, T, H):
     do = _r(B, T, H * 32, seed=31)
     o, lse = A.attn_fwd(qkv, H)
     d_fused = A.attn_bwd(qkv, o, lse, do, H)
-    d_two = A.attn_bwd(qkv, o, lse, do, H, flags=1)
+    assert A.last_launch().kernels == ("attn_bwd_fused_kernel<32>",), A.last_launch()
+    d_two = A.attn_bwd(qkv, o, lse, do, H, flags=A.BwdFlags.TWO_ROUND)
+    assert A.last_launch().kernels == ("attn_bwd_res_kernel<32>",), A.last_launch()
     dref = _attn_ref64(qkv, do, H)[2]  # float64, independent of the GPU's o and lse
     _close(d_fused.cpu().float(), dref, 3e-2, "attn_bwd_fused")
     _close(d_fused.cpu().float(), d_two.cpu().float(), 2e-2, "fused_vs_two_round")
     # deterministic: a second launch is bitwise identical
     assert torch.equal(d_fused, A.attn_bwd(qkv, o, lse, do, H))
+
+
+@pytest.mark.parametrize("B,T,H,hd", [(1, 200, 3, 32), (1, 777, 2, 64), (1, 256, 2, 128)])
+def test_attention_plan_query_is_what_launches(cuda, B, T, H, hd):
+    """A.plan_fwd / A.plan_bwd asked before a call equal A.last_launch() after it, and asking launches and
+    records nothing: the calls that follow a query return the bits they return without one."""
+    qkv = _r(B, T, 3 * H * hd, seed=50)
+    do = _r(B, T, H * hd, seed=51)
+    o0, lse0 = A.attn_fwd(qkv, H)
+    d0 = A.attn_bwd(qkv, o0, lse0, do, H)
+    before = A.last_launch()
+    planned_f, planned_b = A.plan_fwd(B, T, H, hd), A.plan_bwd(B, T, H, hd)
+    assert A.last_launch() == before
+    assert planned_f.direction == "fwd" and planned_b.direction == "bwd" and planned_f.launches and planned_b.launches
+    o, lse = A.attn_fwd(qkv, H)
+    assert A.last_launch() == planned_f
+    d = A.attn_bwd(qkv, o, lse, do, H)
+    assert A.last_launch() == planned_b == before
+    assert torch.equal(o, o0) and torch.equal(lse, lse0) and torch.equal(d, d0)
 
 
 @pytest.mark.parametrize("M,D,V,Vp", [(512, 128, 1000, 1024), (2048, 256, 50258, 50304)])

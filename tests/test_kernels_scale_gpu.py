@@ -142,13 +142,24 @@ def _report(family, shape, spike, name, out, ref, floor):
 RES32 = [(1, 512, 2, 32), (1, 508, 3, 32)]                     # resident: T <= 512 and T % 4 == 0
 CHUNK32 = [(1, 1024, 2, 32), (1, 1000, 2, 32), (1, 203, 3, 32)]  # chunked: T > 512 or T % 4 != 0 (203: odd T)
 HD64 = [(1, 1024, 2, 64), (1, 1000, 2, 64), (1, 777, 3, 64)]
-FWD_FAMILY = {("res32", 0): "attn_fwd_res<32>", ("res32", 1): "attn_fwd_res<32>, plain wave order",
-              ("chunk32", 0): "attn_fwd_chunk<32>", ("hd64", 0): "attn_fwd5<64>, 3 waves/SIMD",
-              ("hd64", 32): "attn_fwd5<64>, 2 waves/SIMD", ("hd64", 16): "attn_fwd32<64>",
-              ("hd64", 4): "attn_fwd_chunk<64>"}
-BWD_FAMILY = {("res32", 0): "attn_bwd_fused<32>", ("res32", 1): "attn_bwd_res<32> (two-round)",
-              ("chunk32", 0): "attn_bwd_{dq,dkdv}_chunk<32>", ("hd64", 0): "attn_bwd_merged32<64>",
-              ("hd64", 8): "attn_bwd_merged32<64>, flag 8", ("hd64", 4): "attn_bwd_{dq,dkdv}_chunk<64>"}
+# the kernels each (kind, flags) case must launch, in order: asserted against A.last_launch() after the call
+FF, BF = A.FwdFlags, A.BwdFlags
+FWD_FAMILY = {("res32", 0): ("attn_fwd_res_kernel<32>",), ("res32", FF.PLAIN_WAVES): ("attn_fwd_res_kernel<32>",),
+              ("chunk32", 0): ("attn_fwd_chunk_kernel<32>",), ("hd64", 0): ("attn_fwd5_kernel<64,3>",),
+              ("hd64", FF.WPS2): ("attn_fwd5_kernel<64,2>",), ("hd64", FF.ROUND4): ("attn_fwd32_kernel<64>",),
+              ("hd64", FF.CHUNK16): ("attn_fwd_chunk_kernel<64>",)}
+BWD_FAMILY = {("res32", 0): ("attn_bwd_fused_kernel<32>",), ("res32", BF.TWO_ROUND): ("attn_bwd_res_kernel<32>",),
+              ("chunk32", 0): ("attn_bwd_dq_chunk_kernel<32>", "attn_bwd_dkdv_chunk_kernel<32>"),
+              ("hd64", 0): ("attn_delta_kernel<64>", "attn_bwd_merged32_kernel<64>"),
+              ("hd64", BF.FORCE_MERGED): ("attn_delta_kernel<64>", "attn_bwd_merged32_kernel<64>"),
+              ("hd64", BF.CHUNK16): ("attn_bwd_dq_chunk_kernel<64>", "attn_bwd_dkdv_chunk_kernel<64>")}
+
+
+def _ran(direction, family, flags):
+    """Asserts the record of the call just made; returns the label of its SCALE lines, from the record."""
+    rec = A.last_launch()
+    assert rec.direction == direction and rec.kernels == family, (rec, family)
+    return " + ".join(rec.kernels) + (f", flags {int(flags)}" if flags else "")
 
 
 def _cases(table):
@@ -162,7 +173,7 @@ FWD_CASES = _cases([("res32", RES32, (0, 1)), ("chunk32", CHUNK32, (0,)), ("hd64
     pytest.param(HD64[0], "hd64", f, True, id=f"1x1024x2x64-hd64-f{f}-spike") for f in (0, 16)]
 # Finding (docs/NUMERICS.md): on the spike input the softmax of the late queries saturates on the spike key, so
 # dS = P (dP - delta) cancels, and delta = rowsum(dO * O) is formed from the forward's bf16-rounded O
-# (csrc/attention.hip launch_attn_delta and the delta passes of the dQ kernels).  That rounding alone -- the float64
+# (csrc/attention.hip attn_delta_kernel and the delta passes of the dQ kernels).  That rounding alone -- the float64
 # emulation with every other step exact -- leaves 7.9e-2 of the block's maximum in dQ (6 of 128 blocks over 3e-2);
 # with an fp32 O the same emulation gives 3.7e-3.  No backward kernel can do better on a bf16 O.
 SPIKE_DQ = pytest.mark.xfail(strict=True, reason="delta = rowsum(dO * O) from the bf16-rounded O: 7.9e-2 per block in "
@@ -181,10 +192,11 @@ def test_attention_fwd_blocks(cuda, shape, kind, flags, spike):
     B, T, H, hd = shape
     qkv, _, ref, floor = _attn_case(B, T, H, hd, spike)
     o, lse = A.attn_fwd(qkv.to(cuda), H, flags=flags)
+    family = _ran("fwd", FWD_FAMILY[kind, flags], flags)
     o = o.view(B, T, H, hd)
-    _report(FWD_FAMILY[kind, flags], shape, spike, "o", o, ref, floor)
+    _report(family, shape, spike, "o", o, ref, floor)
     lse_err = (lse.cpu().double() - ref["lse"]).abs().max().item()
-    print(f"SCALE-LSE | {FWD_FAMILY[kind, flags]} | {shape}{' spike' if spike else ''} | max abs err {lse_err:.3e}")
+    print(f"SCALE-LSE | {family} | {shape}{' spike' if spike else ''} | max abs err {lse_err:.3e}")
     _close_blocks(o, ref["o"], 2e-2, BLOCK, 1, "o")
     assert lse_err <= 1e-3, f"lse: max abs err {lse_err:.3e} > 1e-3"
 
@@ -202,9 +214,10 @@ def test_attention_bwd_blocks(cuda, shape, kind, flags, spike, tensors):
     qkv_d, do_d = qkv.to(cuda), do.to(cuda)
     o, lse = A.attn_fwd(qkv_d, H)
     d = A.attn_bwd(qkv_d, o, lse, do_d, H, flags=flags).view(B, T, 3, H, hd)
+    family = _ran("bwd", BWD_FAMILY[kind, flags], flags)
     outs = {n: d[:, :, "qkv".index(n[1])] for n in tensors}
     for n, t in outs.items():
-        _report(BWD_FAMILY[kind, flags], shape, spike, n, t, ref, floor)
+        _report(family, shape, spike, n, t, ref, floor)
     for n, t in outs.items():
         _close_blocks(t, ref[n], 3e-2, BLOCK, 1, n)
 
