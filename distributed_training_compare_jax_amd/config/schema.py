@@ -77,6 +77,10 @@ are optional and default to the reference behaviour:
   kernels with a lm_head epilogue that stores no logits (``train/engine.py Engine.evaluate``); the training run is bit
   for bit the one without it, and its clock stops for the duration.  pp = 1; not with ``defer_optimizer`` (parameters
   are not final between steps) or ``data: fineweb``.
+* ``TrainConfig.doc_mask_token`` (default -1 = off): the id of the separator token of packed rows.  Attention then
+  stops at document boundaries (a document starts at position 0 and after every separator; positions stay absolute,
+  the loss is unchanged), in training and in evaluation, with bounds computed inside the step program from each
+  (micro)step's ids.  GPU: bf16 at head_dim 64 / 128, pp = 1; ``metrics.json`` records the value.
 """
 
 from __future__ import annotations
@@ -392,8 +396,16 @@ class TrainConfig:
     # one, a forward-only pass over eval_batches held-out batches of `batch` rows -> loss, perplexity, top-1.  0 = off
     eval_every: int = 0
     eval_batches: int = 8
+    # document-masked attention for packed rows: the id of the separator (end-of-text) token.  Position t starts a
+    # document iff t == 0 or ids[t-1] is the separator, and a query sees only the keys of its own document
+    # (ops/attention.py doc_bounds; the separator belongs to the document it ends).  Position embeddings stay
+    # absolute and the loss is unchanged.  -1 = off: nothing is allocated or launched.  GPU: bf16, head_dim 64 / 128,
+    # pp == 1 (train/engine.py refuses the rest by name)
+    doc_mask_token: int = -1
 
     def __post_init__(self):
+        if isinstance(self.doc_mask_token, bool) or not isinstance(self.doc_mask_token, int) or self.doc_mask_token < -1:
+            raise ValueError(f"doc_mask_token={self.doc_mask_token!r}: expected a token id >= 0, or -1 (off)")
         for name in ("eval_every", "eval_batches"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, int) or v < 0:

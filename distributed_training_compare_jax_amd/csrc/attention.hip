@@ -745,10 +745,22 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const bf16* base, lo
   return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)(((long)(T - 1) * stride + width) * 2), 0x00020000);
 }
 
-template <int HD>
-__global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
-                                                              float* __restrict__ lse, int B, int T, int H,
-                                                              float scale) {
+// DOC (attn_fwd32_doc_kernel): causal attention that stops at document boundaries.  doc_start[b, q] is the first
+// key query q may see (int32 [B, T], non-decreasing along q; dtc_doc_bounds).  Per lane a second, lower limit
+// lo = doc_start[b, q]: keys below it get -inf BEFORE the tile max is taken (a masked key never moves the
+// running max, so rows of one document are bitwise independent of every other document), under a wave-uniform
+// flag like `diag` inside the one body -- the select runs only on tiles holding a key below the lo of the wave's
+// last query.  The key-tile loop starts at the tile of doc_start[b, first query of the block] (the block's
+// minimum: the array is monotone) and a wave skips what lies wholly below the lo of its first query.  The LDS
+// fill of tile it + 1 stays unconditional inside the shortened loop.  With DOC = false every doc expression is a
+// compile-time constant and the code is attn_fwd32_kernel's as it was.
+template <int HD, bool DOC>
+__device__ __forceinline__ void fwd32_body(const bf16* qkv, bf16* o, float* lse, const int* doc_start, int B, int T,
+                                           int H, float scale) {
+  // No __restrict__ here: the two wrapper kernels below carry it on their own parameters, which is where the
+  // compiler takes the no-alias facts of a kernel from.  Repeating it on this inlined body would add a second,
+  // scoped set of no-alias metadata at the inlining site, which attn_fwd32_kernel never had while the body was the
+  // kernel itself.
   constexpr int HC = HD / 16, HB = HD / 32;
   using L = FwLds<HD>;
   extern __shared__ __attribute__((aligned(16))) bf16 lds[];
@@ -768,14 +780,30 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
 #pragma unroll
   for (int c = 0; c < HC; ++c) qf[c] = q < T ? *(const bf16x8*)(Qb + (long)q * ts + 16 * c + 8 * hh) : bf16x8{};
   const float cs = scale * LOG2E;
-  float m = -1e30f, l = 0.f;  // m: running max of s * cs (finite start: masked scores give exp2(-inf) = 0)
+  // m: running max of s * cs (finite start: masked scores give exp2(-inf) = 0).  DOC relies on the start being
+  // FINITE: a wave whose first query's document starts before a later lane's processes tiles that are wholly
+  // masked for that lane (the causal-only kernel never does); there mt = -inf, m stays -1e30, alpha = exp2(0) = 1
+  // and every P = exp2(-inf + 1e30) = 0.  With m = -INFINITY the same lane would compute exp2(-inf + inf) = NaN.
+  float m = -1e30f, l = 0.f;
   f32x16 acc[HB];
 #pragma unroll
   for (int i = 0; i < HB; ++i) acc[i] = f32x16{};
   const int qlim = min(q, T - 1);  // last key this lane's query may see
+  // DOC: lo = first key this lane's query may see; lo_w0 / lo_w1 = that of the wave's first / last query (rows
+  // >= T are never read); it0 = first key tile any query of the block sees
+  int lo = 0, lo_w0 = 0, lo_w1 = 0, it0 = 0;
+  if constexpr (DOC) {
+    const int* ds = doc_start + (long)b * T;
+    lo = ds[qlim];
+    lo_w0 = __builtin_amdgcn_readfirstlane(ds[min(q0, T - 1)]);
+    lo_w1 = __builtin_amdgcn_readfirstlane(ds[min(q0 + 31, T - 1)]);
+    it0 = __builtin_amdgcn_readfirstlane(ds[qblk * FW_QROWS]) / FW_KEYS;
+    DTC_ASSERT(lo >= 0 && lo <= qlim && lo_w0 <= lo && lo <= lo_w1 && it0 >= 0);
+  }
 
-  // one 64-key tile; MASK: the tile crosses this wave's diagonal (or the sequence end)
-  auto tile = [&](const bf16* sK, const bf16* sV, int kb, auto MASK) {
+  // one 64-key tile; MASK: the tile crosses this wave's diagonal (or the sequence end); low (DOC): it holds a key
+  // below some query's lo
+  auto tile = [&](const bf16* sK, const bf16* sV, int kb, auto MASK, bool low) {
     f32x16 sc[2];
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) {
@@ -790,6 +818,16 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
         const int lim = qlim - (kb + 32 * k2 + 4 * hh);  // keep key offset (i&3) + 8(i>>2) <= lim
 #pragma unroll
         for (int i = 0; i < 16; ++i) sc[k2][i] = ((i & 3) + 8 * (i >> 2) <= lim) ? sc[k2][i] : -INFINITY;
+      }
+    }
+    if constexpr (DOC) {
+      if (low) {
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const int llim = lo - (kb + 32 * k2 + 4 * hh);  // keep key offset (i&3) + 8(i>>2) >= llim
+#pragma unroll
+          for (int i = 0; i < 16; ++i) sc[k2][i] = ((i & 3) + 8 * (i >> 2) >= llim) ? sc[k2][i] : -INFINITY;
+        }
       }
     }
     float mt = sc[0][0];
@@ -831,7 +869,7 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
   // K fragments live beside the 64-register O accumulator and spills at 2 waves per SIMD), the diagonal mask
   // under a wave-uniform branch inside ONE body.  Per block 8 QK^T + 8 PV MFMAs against 16 exponentials
   // per lane: twice the MFMA work per softmax element of head_dim 64.
-  auto block = [&](const bf16* sK, const bf16* sV, int k2, int ks, bool diag) {
+  auto block = [&](const bf16* sK, const bf16* sV, int k2, int ks, bool diag, bool low) {
     f32x16 sc = f32x16{};
 #pragma unroll
     for (int c = 0; c < HC; ++c)
@@ -840,6 +878,13 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
       const int lim = qlim - (ks + 4 * hh);  // keep key offset (i&3) + 8(i>>2) <= lim
 #pragma unroll
       for (int i = 0; i < 16; ++i) sc[i] = ((i & 3) + 8 * (i >> 2) <= lim) ? sc[i] : -INFINITY;
+    }
+    if constexpr (DOC) {
+      if (low) {
+        const int llim = lo - (ks + 4 * hh);  // keep key offset (i&3) + 8(i>>2) >= llim
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sc[i] = ((i & 3) + 8 * (i >> 2) >= llim) ? sc[i] : -INFINITY;
+      }
     }
     float mt = sc[0];
 #pragma unroll
@@ -880,24 +925,26 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
       *(u32x4*)(sV + rr * L::VLD + col) = rs.y[i];
     }
   };
-  rs.load(rK, ts, rV, ts, 0, tid);
-  store(0);
+  rs.load(rK, ts, rV, ts, it0 * FW_KEYS, tid);
+  store(it0 & 1);
   __syncthreads();
-  for (int it = 0; it < nkt; ++it) {
+  for (int it = it0; it < nkt; ++it) {
     if (it + 1 < nkt) rs.load(rK, ts, rV, ts, (it + 1) * FW_KEYS, tid);
     const int kb = it * FW_KEYS;
     const bf16* sK = lds + (it & 1) * L::STAGE;
-    if (kb <= q0 + 31 && q0 < T) {  // wave-uniform: else the whole tile lies past this wave's queries
+    // wave-uniform: else the whole tile lies past this wave's queries (DOC: or before the first one's document)
+    if (kb <= q0 + 31 && q0 < T && (!DOC || kb + FW_KEYS - 1 >= lo_w0)) {
       if constexpr (HD == 128) {
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
           const int ks = kb + 32 * k2;
           if (ks > q0 + 31) break;  // wave-uniform: these 32 keys lie past every query of the wave
-          block(sK, sK + FW_KEYS * L::KLD, k2, ks, ks + 31 > q0);
+          if (DOC && ks + 31 < lo_w0) continue;  // wave-uniform: ... or before every query's document
+          block(sK, sK + FW_KEYS * L::KLD, k2, ks, ks + 31 > q0, DOC && ks < lo_w1);
         }
       } else {
-        if (kb + FW_KEYS - 1 > q0) tile(sK, sK + FW_KEYS * L::KLD, kb, std::true_type{});
-        else tile(sK, sK + FW_KEYS * L::KLD, kb, std::false_type{});
+        if (kb + FW_KEYS - 1 > q0) tile(sK, sK + FW_KEYS * L::KLD, kb, std::true_type{}, DOC && kb < lo_w1);
+        else tile(sK, sK + FW_KEYS * L::KLD, kb, std::false_type{}, DOC && kb < lo_w1);
       }
     }
     if (it + 1 < nkt) store((it + 1) & 1);
@@ -916,6 +963,19 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* _
                    f2bf(acc[i][4 * g4 + 3] * inv)};
     if (hh == 0) lse[((long)b * H + h) * T + q] = (m + __log2f(l)) * LN2;
   }
+}
+
+template <int HD>
+__global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
+                                                              float* __restrict__ lse, int B, int T, int H,
+                                                              float scale) {
+  fwd32_body<HD, false>(qkv, o, lse, nullptr, B, T, H, scale);
+}
+template <int HD>
+__global__ void __launch_bounds__(FW_THREADS, 2) attn_fwd32_doc_kernel(
+    const bf16* __restrict__ qkv, bf16* __restrict__ o, float* __restrict__ lse, const int* __restrict__ doc_start,
+    int B, int T, int H, float scale) {
+  fwd32_body<HD, true>(qkv, o, lse, doc_start, B, T, H, scale);
 }
 
 // ---------------------------------------------------------------------------- forward, round 5 pipeline
@@ -1217,11 +1277,14 @@ __device__ __forceinline__ void sw_pipelined_tiles(int n, T0 t0_of, __amdgpu_buf
 // dO stationary in registers), dS^T = P^T (dP^T - delta) in registers, dQ^T += K^T dS^T (K transposed
 // fragments, dS^T straight from the accumulators).
 // DELTA_IN (the merged launch): delta comes precomputed (attn_delta_kernel) instead of from O here.
-template <int HD, bool DELTA_IN>
+// DOC (the doc-masked kernels, see fwd32_body): the forward's lower limit lo = doc_start[b, q] -- P of keys below
+// it is zeroed by select (never by multiply: exp2 of a score against another document's lse may be inf) under a
+// wave-uniform flag -- and the forward's loop start and wave skip.
+template <int HD, bool DELTA_IN, bool DOC = false>
 __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv, const bf16* __restrict__ o,
                                           const bf16* __restrict__ dout, const float* __restrict__ lse,
                                           float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int T, int H,
-                                          float scale) {
+                                          float scale, const int* __restrict__ doc_start = nullptr) {
   static_assert(HD == 64 || HD == 128, "swizzled 64- / 128-wide images");
   constexpr int HC = HD / 16, HB = HD / 32;
   extern __shared__ __attribute__((aligned(16))) bf16 lds[];
@@ -1265,7 +1328,16 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
   // body (two instantiations of the whole block joined with 16 v_mov_b64 copies of the dQ accumulators per
   // block: 79.4 -> 78.7 us per merged backward, profiles/r5_attention.md).  Keys >= T only meet queries >= T
   // (key <= q), whose rows are never written, and load as zeros (buffer range): the causal mask suffices.
-  auto kblock = [&](const bf16* sK, const bf16* sV, int k2, int ks, bool diag) {
+  int lo = 0, lo_w0 = 0, lo_w1 = 0, it0 = 0;  // DOC: as in fwd32_body
+  if constexpr (DOC) {
+    const int* ds = doc_start + (long)b * T;
+    lo = ds[min(q, T - 1)];
+    lo_w0 = __builtin_amdgcn_readfirstlane(ds[min(q0, T - 1)]);
+    lo_w1 = __builtin_amdgcn_readfirstlane(ds[min(q0 + 31, T - 1)]);
+    it0 = __builtin_amdgcn_readfirstlane(ds[qblk * FW_QROWS]) / 64;
+    DTC_ASSERT(lo >= 0 && lo <= min(q, T - 1) && lo_w0 <= lo && lo <= lo_w1 && it0 >= 0);
+  }
+  auto kblock = [&](const bf16* sK, const bf16* sV, int k2, int ks, bool diag, bool low) {
     f32x16 st = f32x16{}, dp = f32x16{};
     int ln = lane;
     if constexpr (HD == 128) {
@@ -1293,6 +1365,13 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
 #pragma unroll
       for (int i = 0; i < 16; ++i) st[i] = ((i & 3) + 8 * (i >> 2) <= lim) ? st[i] : 0.f;
     }
+    if constexpr (DOC) {
+      if (low) {
+        const int llim = lo - (ks + 4 * hh);  // keep key offset (i&3) + 8(i>>2) >= llim
+#pragma unroll
+        for (int i = 0; i < 16; ++i) st[i] = ((i & 3) + 8 * (i >> 2) >= llim) ? st[i] : 0.f;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 16; ++i) st[i] *= dp[i] - dlt;
 #pragma unroll
@@ -1304,18 +1383,21 @@ __device__ __forceinline__ void dq32_body(int bid, const bf16* __restrict__ qkv,
     }
   };
   auto body = [&](const bf16* sK, const bf16* sV, const float*, int it) {
-    const int kb = it * 64;
+    const int kb = (it0 + it) * 64;
     if (kb > q0 + 31 || q0 >= T) return;
+    if (DOC && kb + 63 < lo_w0) return;  // wave-uniform: every key of the tile before the first query's document
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) {
       const int ks = kb + 32 * k2;
       if (ks > q0 + 31) break;  // wave-uniform: these 32 keys lie past every query
-      kblock(sK, sV, k2, ks, ks + 31 > q0);
+      if (DOC && ks + 31 < lo_w0) continue;  // wave-uniform: ... or before every query's document
+      kblock(sK, sV, k2, ks, ks + 31 > q0, DOC && ks < lo_w1);
     }
   };
   const int nkt = (min(T, qblk * FW_QROWS + FW_QROWS) + 63) / 64;
-  sw_pipelined_tiles<FW_THREADS, false, HD>(nkt, [](int it) { return it * 64; }, rows_rsrc(Kb, ts, T, HD), ts,
-                                            rows_rsrc(Vb, ts, T, HD), ts, nullptr, nullptr, T, lds, tid, body);
+  sw_pipelined_tiles<FW_THREADS, false, HD>(nkt - it0, [it0](int it) { return (it0 + it) * 64; },
+                                            rows_rsrc(Kb, ts, T, HD), ts, rows_rsrc(Vb, ts, T, HD), ts, nullptr,
+                                            nullptr, T, lds, tid, body);
   if (q < T) {
     bf16* pq = dqkv + ((long)b * T + q) * ts + (0 * H + h) * HD;
 #pragma unroll
@@ -1335,15 +1417,28 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_bwd_dq32_kernel(
     float scale) {
   dq32_body<HD, DELTA_IN>((int)blockIdx.x, qkv, o, dout, lse, delta, dqkv, B, T, H, scale);
 }
+// doc-masked dQ (delta precomputed by attn_delta_kernel)
+template <int HD>
+__global__ void __launch_bounds__(FW_THREADS, 2) attn_bwd_dq32_doc_kernel(
+    const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const float* __restrict__ lse,
+    float* __restrict__ delta, bf16* __restrict__ dqkv, const int* __restrict__ doc_start, int B, int T, int H,
+    float scale) {
+  dq32_body<HD, true, true>((int)blockIdx.x, qkv, nullptr, dout, lse, delta, dqkv, B, T, H, scale, doc_start);
+}
 
 // dK, dV: block = 4 waves = 128 keys of one (b, h); wave = 32 keys on the lane.  Per 32-query block:
 // S = Q K^T and dP = dO V^T (Q / dO row fragments, K / V stationary), P and dS = P (dP - delta) with the
 // key on the lane, dV^T += dO^T P and dK^T += Q^T dS (Q / dO transposed fragments of the same images,
 // P / dS straight from the accumulators).  The heaviest key block (0: every query) goes first.
-template <int HD>
+// DOC (the doc-masked kernels): hi = doc_end[b, key], one past the last query that sees this lane's key (int32
+// [B, T], non-decreasing along the key).  P of queries >= hi is zeroed by select under a wave-uniform flag, the
+// query-tile loop ends at the doc_end of the block's last key, and a wave skips what lies at or past the hi of
+// its last key.
+template <int HD, bool DOC = false>
 __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                             const float* __restrict__ lse, const float* __restrict__ delta,
-                                            bf16* __restrict__ dqkv, int B, int T, int H, float scale) {
+                                            bf16* __restrict__ dqkv, int B, int T, int H, float scale,
+                                            const int* __restrict__ doc_end = nullptr) {
   static_assert(HD == 64 || HD == 128, "swizzled 64- / 128-wide images");
   constexpr int HC = HD / 16, HB = HD / 32;
   extern __shared__ __attribute__((aligned(16))) bf16 lds[];
@@ -1372,11 +1467,22 @@ __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qk
 #pragma unroll
   for (int i = 0; i < HB; ++i) dk[i] = dv[i] = f32x16{};
   const int qt0 = kblk * FW_QROWS / 64;  // first 64-query tile (queries >= the block's keys)
+  // DOC: hi = one past the last query that sees this lane's key; hi_w0 / hi_w1 = that of the wave's first / last
+  // key; qend = that of the block's last key (rows >= T are never read)
+  int hi = T, hi_w0 = T, hi_w1 = T, qend = T;
+  if constexpr (DOC) {
+    const int* de = doc_end + (long)b * T;
+    hi = de[min(key, T - 1)];
+    hi_w0 = __builtin_amdgcn_readfirstlane(de[min(k0w, T - 1)]);
+    hi_w1 = __builtin_amdgcn_readfirstlane(de[min(k0w + 31, T - 1)]);
+    qend = __builtin_amdgcn_readfirstlane(de[min(kblk * FW_QROWS + FW_QROWS - 1, T - 1)]);
+    DTC_ASSERT(hi <= T && hi > min(key, T - 1) && hi_w0 <= hi && hi <= hi_w1 && hi_w1 <= qend && qend <= T);
+  }
   // one 32-query block; the causal mask (key <= query) only where the block straddles the wave's keys,
   // under a wave-uniform branch inside ONE body (as the forward / dQ: no second register assignment).
   // Queries >= T need no mask: their Q / dO rows load as zeros (buffer range) and lse / delta as 0, so
   // they add nothing to dK / dV; keys >= T are never written.
-  auto qblock = [&](const bf16* sQ, const bf16* sD, const float* sv, int k2, int qs, bool diag) {
+  auto qblock = [&](const bf16* sQ, const bf16* sD, const float* sv, int k2, int qs, bool diag, bool high) {
     f32x16 sc = f32x16{}, dp = f32x16{};
 #pragma unroll
     for (int c = 0; c < HC; ++c) {
@@ -1400,6 +1506,13 @@ __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qk
 #pragma unroll
       for (int i = 0; i < 16; ++i) sc[i] = ((i & 3) + 8 * (i >> 2) >= lim) ? sc[i] : 0.f;
     }
+    if constexpr (DOC) {
+      if (high) {
+        const int hlim = hi - (qs + 4 * hh);  // keep query offset (i&3) + 8(i>>2) < hlim
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sc[i] = ((i & 3) + 8 * (i >> 2) < hlim) ? sc[i] : 0.f;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 16; ++i) ds[i] *= sc[i];
 #pragma unroll
@@ -1415,14 +1528,17 @@ __device__ __forceinline__ void dkdv32_body(int bid, const bf16* __restrict__ qk
   auto body = [&](const bf16* sQ, const bf16* sD, const float* sv, int it) {
     const int qb = (qt0 + it) * 64;
     if (qb + 63 < k0w || k0w >= T) return;  // wave-uniform: every query of the tile before the keys
+    if (DOC && qb >= hi_w1) return;         // wave-uniform: ... or past the last key's document
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) {
       const int qs = qb + 32 * k2;
       if (qs + 31 < k0w || qs >= T) continue;  // wave-uniform
-      qblock(sQ, sD, sv, k2, qs, qs < k0w + 31);  // wave-uniform: some query of the block precedes a key
+      if (DOC && qs >= hi_w1) continue;        // wave-uniform
+      // wave-uniform: some query of the block precedes a key; DOC: some query lies past the first key's document
+      qblock(sQ, sD, sv, k2, qs, qs < k0w + 31, DOC && qs + 31 >= hi_w0);
     }
   };
-  const int nqt = (T - qt0 * 64 + 63) / 64;
+  const int nqt = (qend - qt0 * 64 + 63) / 64;
   sw_pipelined_tiles<FW_THREADS, true, HD>(nqt, [qt0](int it) { return (qt0 + it) * 64; }, rows_rsrc(Qb, ts, T, HD),
                                            ts, rows_rsrc(dOb, dts, T, HD), dts, lseb, delb, T, lds, tid, body);
   if (key < T) {
@@ -1452,6 +1568,13 @@ __global__ void __launch_bounds__(FW_THREADS, HD == 128 ? 1 : 2) attn_bwd_dkdv32
     const float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int T, int H, float scale) {
   dkdv32_body<HD>((int)blockIdx.x, qkv, dout, lse, delta, dqkv, B, T, H, scale);
 }
+template <int HD>
+__global__ void __launch_bounds__(FW_THREADS, HD == 128 ? 1 : 2) attn_bwd_dkdv32_doc_kernel(
+    const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const float* __restrict__ lse,
+    const float* __restrict__ delta, bf16* __restrict__ dqkv, const int* __restrict__ doc_end, int B, int T, int H,
+    float scale) {
+  dkdv32_body<HD, true>((int)blockIdx.x, qkv, dout, lse, delta, dqkv, B, T, H, scale, doc_end);
+}
 
 // dK/dV and dQ blocks in ONE launch (delta precomputed by attn_delta_kernel): the dK/dV blocks first,
 // then the dQ blocks, each heaviest first, so the second kernel's blocks fill the first one's tail
@@ -1463,6 +1586,15 @@ __global__ void __launch_bounds__(FW_THREADS, 2) attn_bwd_merged32_kernel(
   const int bid = (int)blockIdx.x;
   if (bid < nk) dkdv32_body<HD>(bid, qkv, dout, lse, delta, dqkv, B, T, H, scale);
   else dq32_body<HD, true>(bid - nk, qkv, nullptr, dout, lse, delta, dqkv, B, T, H, scale);
+}
+template <int HD>
+__global__ void __launch_bounds__(FW_THREADS, 2) attn_bwd_merged32_doc_kernel(
+    const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const float* __restrict__ lse,
+    float* __restrict__ delta, bf16* __restrict__ dqkv, const int* __restrict__ doc_start,
+    const int* __restrict__ doc_end, int B, int T, int H, float scale, int nk) {
+  const int bid = (int)blockIdx.x;
+  if (bid < nk) dkdv32_body<HD, true>(bid, qkv, dout, lse, delta, dqkv, B, T, H, scale, doc_end);
+  else dq32_body<HD, true, true>(bid - nk, qkv, nullptr, dout, lse, delta, dqkv, B, T, H, scale, doc_start);
 }
 
 // Chunked backward for T > RES_MAXT / head_dim 64 (the tiled kernels above with 16 waves = 256
@@ -2149,14 +2281,17 @@ int attn_cu_count() {
 // dynamic LDS bytes of the kernels sized by their layout structs (0: the plan already holds the size)
 int layout_lds_bytes(int kernel) {
   switch (kernel) {
-    case ap::K_FWD32_128: return fw_lds_bytes<128>();
-    case ap::K_FWD32_64: case ap::K_FWD5_64_2: case ap::K_FWD5_64_3: return fw_lds_bytes<64>();
+    case ap::K_FWD32_128: case ap::K_FWD32_DOC_128: return fw_lds_bytes<128>();
+    case ap::K_FWD32_64: case ap::K_FWD5_64_2: case ap::K_FWD5_64_3: case ap::K_FWD32_DOC_64: return fw_lds_bytes<64>();
     case ap::K_FWD_CHUNK_32: return ch_lds_fwd<32>();
     case ap::K_FWD_CHUNK_64: return ch_lds_fwd<64>();
     case ap::K_BWD_DQ_CHUNK_32: case ap::K_BWD_DKDV_CHUNK_32: return ch_lds_bwd<32>();
     case ap::K_BWD_DQ_CHUNK_64: case ap::K_BWD_DKDV_CHUNK_64: return ch_lds_bwd<64>();
-    case ap::K_BWD_DQ32_64: case ap::K_BWD_DKDV32_64: case ap::K_BWD_MERGED32_64: return 2 * SW_STAGE * 2;
-    case ap::K_BWD_DQ32_128_DELTA_IN: case ap::K_BWD_DKDV32_128: return 2 * sw_stage<128>() * 2;
+    case ap::K_BWD_DQ32_64: case ap::K_BWD_DKDV32_64: case ap::K_BWD_MERGED32_64: case ap::K_BWD_MERGED32_DOC_64:
+      return 2 * SW_STAGE * 2;
+    case ap::K_BWD_DQ32_128_DELTA_IN: case ap::K_BWD_DKDV32_128: case ap::K_BWD_DQ32_DOC_128:
+    case ap::K_BWD_DKDV32_DOC_128:
+      return 2 * sw_stage<128>() * 2;
     default: return 0;
   }
 }
@@ -2170,6 +2305,12 @@ ap::AttnPlan plan_fwd(int B, int T, int H, int HD, int flags, int cus) {
 }
 ap::AttnPlan plan_bwd(int B, int T, int H, int HD, int flags, long ws_bytes, int cus) {
   return with_layout_lds(ap::plan_attn_bwd(B, T, H, HD, flags, ws_bytes, cus, g_attn_knobs));
+}
+ap::AttnPlan plan_fwd_doc(int B, int T, int H, int HD, int flags, int cus) {
+  return with_layout_lds(ap::plan_attn_fwd_doc(B, T, H, HD, flags, cus, g_attn_knobs));
+}
+ap::AttnPlan plan_bwd_doc(int B, int T, int H, int HD, int flags, long ws_bytes, int cus) {
+  return with_layout_lds(ap::plan_attn_bwd_doc(B, T, H, HD, flags, ws_bytes, cus, g_attn_knobs));
 }
 
 // fw_order is a pure function of these four; the last one asked for is kept per host thread
@@ -2204,7 +2345,11 @@ FwOrder cached_fw_order(int nqb, int nbh, int wps, int cus) {
     (const void*)attn_bwd_dkdv_chunk_kernel<64>, (const void*)attn_bwd_dq_chunk_kernel<64>,
     (const void*)attn_bwd_dkdv_chunk_kernel<32>, (const void*)attn_bwd_dq_chunk_kernel<32>,
     (const void*)attn_delta_kernel<32>, (const void*)attn_bwd_dkdv_kernel<32>, (const void*)attn_bwd_dq_kernel<32>,
-    (const void*)attn_bwd_dkdv_kernel<64>, (const void*)attn_bwd_dq_kernel<64>};
+    (const void*)attn_bwd_dkdv_kernel<64>, (const void*)attn_bwd_dq_kernel<64>,
+    // the doc-masked kernels, after everything the code object has always had
+    (const void*)attn_fwd32_doc_kernel<64>, (const void*)attn_fwd32_doc_kernel<128>,
+    (const void*)attn_bwd_dq32_doc_kernel<128>, (const void*)attn_bwd_dkdv32_doc_kernel<128>,
+    (const void*)attn_bwd_merged32_doc_kernel<64>};
 #endif
 // one planned launch `l` of `kernel` on the stream `st` of the enclosing entry point
 #define ATTN_LAUNCH(kernel, l, ...)                                                            \
@@ -2333,6 +2478,60 @@ int dtc_attn_bwd(const bf16* qkv, const bf16* o, const float* lse, const bf16* d
   g_attn_last = p;
   DTC_CHECK_LAUNCH();
   return 0;
+}
+
+// Document-masked causal attention: query q of row b sees key k iff doc_start[b, q] <= k <= q, equivalently
+// k <= q < doc_end[b, k] (int32 [B, T] each, dtc_doc_bounds).  head_dim 64 and 128 only (else 4005, nothing
+// launched and nothing recorded); flags and knobs choose nothing here (ap::plan_attn_fwd_doc).
+int dtc_attn_fwd_doc(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, int head_dim, int flags, float scale,
+                     const int* doc_start, const int* doc_end, hipStream_t st) {
+  (void)doc_end;  // the forward masks by the query's document start alone
+  const ap::AttnPlan p = plan_fwd_doc(B, T, H, head_dim, flags, attn_cu_count());
+  if (p.err) return p.err;
+  const ap::Launch& l = p.launch[0];
+  switch (p.path) {
+    case ap::FWD_ROWS32_DOC:
+      if (head_dim == 128) ATTN_LAUNCH(attn_fwd32_doc_kernel<128>, l, qkv, o, lse, doc_start, B, T, H, scale);
+      else ATTN_LAUNCH(attn_fwd32_doc_kernel<64>, l, qkv, o, lse, doc_start, B, T, H, scale);
+      break;
+    default: return 4004;
+  }
+  g_attn_last = p;
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+int dtc_attn_bwd_doc(const bf16* qkv, const bf16* o, const float* lse, const bf16* dout, bf16* dqkv, int flags, int B,
+                     int T, int H, int head_dim, float scale, float* ws, long ws_bytes, const int* doc_start,
+                     const int* doc_end, hipStream_t st) {
+  const ap::AttnPlan p = plan_bwd_doc(B, T, H, head_dim, flags, ws_bytes, attn_cu_count());
+  if (p.err) return p.err;
+  const ap::Launch* l = p.launch;
+  switch (p.path) {
+    case ap::BWD_ROWS32_DOC_128:
+      ATTN_LAUNCH(attn_delta_kernel<128>, l[0], o, dout, ws, B, T, H);
+      ATTN_LAUNCH(attn_bwd_dkdv32_doc_kernel<128>, l[1], qkv, dout, lse, ws, dqkv, doc_end, B, T, H, scale);
+      ATTN_LAUNCH(attn_bwd_dq32_doc_kernel<128>, l[2], qkv, dout, lse, ws, dqkv, doc_start, B, T, H, scale);
+      break;
+    case ap::BWD_ROWS32_DOC_MERGED:
+      ATTN_LAUNCH(attn_delta_kernel<64>, l[0], o, dout, ws, B, T, H);
+      ATTN_LAUNCH(attn_bwd_merged32_doc_kernel<64>, l[1], qkv, dout, lse, ws, dqkv, doc_start, doc_end, B, T, H, scale,
+                  l[1].grid / 2);
+      break;
+    default: return 4004;
+  }
+  g_attn_last = p;
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
+
+// dtc_attn_plan for the document-masked calls
+int dtc_attn_plan_doc(int dir, int B, int T, int H, int HD, int flags, long ws_bytes, int* out) {
+  const int cus = attn_cu_count();
+  const ap::AttnPlan p =
+      dir == ap::DIR_BWD ? plan_bwd_doc(B, T, H, HD, flags, ws_bytes, cus) : plan_fwd_doc(B, T, H, HD, flags, cus);
+  ap::to_record(p, out);
+  return p.err;
 }
 
 // What the matching call would return and record, without launching: dir 1 = dtc_attn_fwd (ws_bytes unused),

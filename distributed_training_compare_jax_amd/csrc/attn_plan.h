@@ -85,6 +85,10 @@ enum Path {
   BWD_ROWS32_SPLIT,  // attn_bwd_dq32<64> (writes delta), attn_bwd_dkdv32<64>
   BWD_CHUNK,         // attn_bwd_dq_chunk (writes delta), attn_bwd_dkdv_chunk, <32 / 64>
   BWD_TILED,         // delta, attn_bwd_dkdv, attn_bwd_dq, <32 / 64>
+  // document-masked attention (plan_attn_fwd_doc / plan_attn_bwd_doc): the 32-row family with per-row bounds
+  FWD_ROWS32_DOC,        // attn_fwd32_doc<64 / 128>
+  BWD_ROWS32_DOC_128,    // delta, attn_bwd_dkdv32_doc<128>, attn_bwd_dq32_doc<128>
+  BWD_ROWS32_DOC_MERGED, // delta, attn_bwd_merged32_doc<64>
   PATH_COUNT,
 };
 
@@ -107,6 +111,9 @@ enum Kernel {
   K_BWD_DQ32_64, K_BWD_DQ32_128_DELTA_IN,
   K_BWD_DKDV32_64, K_BWD_DKDV32_128,
   K_BWD_MERGED32_64,
+  K_FWD32_DOC_64, K_FWD32_DOC_128,
+  K_BWD_DQ32_DOC_128, K_BWD_DKDV32_DOC_128,
+  K_BWD_MERGED32_DOC_64,
   K_COUNT,
 };
 constexpr const char* KERNEL_NAMES[] = {
@@ -126,6 +133,9 @@ constexpr const char* KERNEL_NAMES[] = {
     "attn_bwd_dq32_kernel<64>", "attn_bwd_dq32_kernel<128,true>",
     "attn_bwd_dkdv32_kernel<64>", "attn_bwd_dkdv32_kernel<128>",
     "attn_bwd_merged32_kernel<64>",
+    "attn_fwd32_doc_kernel<64>", "attn_fwd32_doc_kernel<128>",
+    "attn_bwd_dq32_doc_kernel<128>", "attn_bwd_dkdv32_doc_kernel<128>",
+    "attn_bwd_merged32_doc_kernel<64>",
 };
 static_assert(sizeof(KERNEL_NAMES) / sizeof(KERNEL_NAMES[0]) == K_COUNT, "one name per kernel id");
 
@@ -202,7 +212,8 @@ struct Launch {
 constexpr int MAX_LAUNCHES = 3;
 
 struct AttnPlan {
-  int err = 0;  // the code the entry point returns instead of launching: 4001 head_dim, 4002 workspace
+  int err = 0;  // the code the entry point returns instead of launching: 4001 head_dim, 4002 workspace,
+                // 4005 head_dim of a document-masked call (ERR_DOC_HEAD_DIM)
   int dir = DIR_NONE, path = PATH_NONE;
   int order = ORDER_NONE;  // the block order asked of attn_fwd5<64, 3>
   int order_n = 0;         // ORDER_BALANCED: blocks per XCD of the order; 0 = not one round, runs heavy-first
@@ -332,6 +343,45 @@ inline AttnPlan plan_attn_bwd(int B, int T, int H, int HD, int flags, long ws_by
     p.path = BWD_ROWS32_SPLIT;
     p.add(K_BWD_DQ32_64, g32, FW_THREADS);
     p.add(K_BWD_DKDV32_64, g32, FW_THREADS);
+  }
+  return p;
+}
+
+// ---- document-masked attention ----------------------------------------------------------------------------
+// Causal attention that stops at document boundaries (doc_start / doc_end per row, csrc/elementwise.hip
+// dtc_doc_bounds) runs the doc instantiations of the 32-row family at head_dim 64 and 128, whatever the flags and
+// the knobs say: one forward kernel; backward as the unmasked twin's structure (head_dim 64: delta pass + the merged
+// dK/dV + dQ launch, head_dim 128: delta, dK/dV, dQ).  Block order heavy-first by query / key block, as the twins.
+// Any other head_dim (32 included) is refused with ERR_DOC_HEAD_DIM before the workspace is looked at.
+constexpr int ERR_DOC_HEAD_DIM = 4005;
+
+inline AttnPlan plan_attn_fwd_doc(int B, int T, int H, int HD, int flags, int cus, const AttnKnobs& k) {
+  (void)flags; (void)cus; (void)k;
+  if (HD != 64 && HD != 128) return refused(DIR_FWD, ERR_DOC_HEAD_DIM);
+  AttnPlan p;
+  p.dir = DIR_FWD;
+  p.path = FWD_ROWS32_DOC;
+  p.add(HD == 128 ? K_FWD32_DOC_128 : K_FWD32_DOC_64, (long)B * H * cdiv(T, FW_QROWS), FW_THREADS);
+  return p;
+}
+
+inline AttnPlan plan_attn_bwd_doc(int B, int T, int H, int HD, int flags, long ws_bytes, int cus, const AttnKnobs& k) {
+  (void)flags; (void)cus; (void)k;
+  if (HD != 64 && HD != 128) return refused(DIR_BWD, ERR_DOC_HEAD_DIM);
+  if (ws_bytes < bwd_workspace_bytes(B, T, H)) return refused(DIR_BWD, 4002);
+  AttnPlan p;
+  p.dir = DIR_BWD;
+  const long bh = (long)B * H, g32 = bh * cdiv(T, FW_QROWS);
+  const long delta_grid = cdiv(bh * T * (HD / 8), 256);
+  if (HD == 128) {
+    p.path = BWD_ROWS32_DOC_128;
+    p.add(K_DELTA_128, delta_grid, 256);
+    p.add(K_BWD_DKDV32_DOC_128, g32, FW_THREADS);
+    p.add(K_BWD_DQ32_DOC_128, g32, FW_THREADS);
+  } else {
+    p.path = BWD_ROWS32_DOC_MERGED;
+    p.add(K_DELTA_64, delta_grid, 256);
+    p.add(K_BWD_MERGED32_DOC_64, 2 * g32, FW_THREADS);
   }
   return p;
 }

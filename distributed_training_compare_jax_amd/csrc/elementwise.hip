@@ -961,11 +961,77 @@ __global__ void __launch_bounds__(256) transpose_batch_kernel(TrBatch batch) {
   }
 }
 
+// ---------------------------------------------------------------------------- document bounds
+// Packed rows: position t starts a document iff t == 0 or ids[t - 1] == sep (the separator belongs to the
+// document it ends).  doc_start[t] = the largest start <= t, doc_end[t] = the smallest start > t, or T: the two
+// limits of document-masked attention (csrc/attention.hip: query q sees key k iff doc_start[q] <= k <= q, i.e.
+// k <= q < doc_end[k]).  One block per row; per chunk of DOC_THREADS positions a block-wide inclusive max-scan
+// from the left (doc_start) and min-scan from the right (doc_end), the running value carried across chunks, so
+// any T >= 1.  No atomics and no host round trip: it sits inside a captured step and reads its static ids.
+constexpr int DOC_THREADS = 256;
+
+template <bool MAX>
+__device__ __forceinline__ int doc_pick(int a, int b) {
+  return MAX ? max(a, b) : min(a, b);
+}
+// inclusive scan of v over the block: towards higher tid (MAX) or towards lower tid (!MAX).  Ends with the result
+// readable by every thread in s[0]; the caller syncs before the next scan overwrites it.
+template <bool MAX>
+__device__ __forceinline__ void doc_scan(int (*s)[DOC_THREADS], int tid, int v) {
+  s[0][tid] = v;
+  __syncthreads();
+  int cur = 0;
+#pragma unroll
+  for (int d = 1; d < DOC_THREADS; d <<= 1) {
+    int x = s[cur][tid];
+    const int other = MAX ? tid - d : tid + d;
+    if (other >= 0 && other < DOC_THREADS) x = doc_pick<MAX>(x, s[cur][other]);
+    s[cur ^ 1][tid] = x;
+    __syncthreads();
+    cur ^= 1;
+  }
+  static_assert(DOC_THREADS == 256, "an even number of steps leaves the result in s[0]");
+}
+
+__global__ void __launch_bounds__(DOC_THREADS) doc_bounds_kernel(const int* __restrict__ ids, int* __restrict__ doc_start,
+                                                                 int* __restrict__ doc_end, int T, int sep) {
+  __shared__ int s[2][DOC_THREADS];
+  const int tid = threadIdx.x;
+  const long row = (long)blockIdx.x * T;
+  ids += row; doc_start += row; doc_end += row;
+  int carry = 0;  // position 0 starts a document
+  for (int c0 = 0; c0 < T; c0 += DOC_THREADS) {
+    const int t = c0 + tid;
+    const int v = t < T && (t == 0 || ids[t - 1] == sep) ? t : -1;
+    doc_scan<true>(s, tid, v);
+    if (t < T) doc_start[t] = max(s[0][tid], carry);
+    carry = max(carry, s[0][DOC_THREADS - 1]);
+    __syncthreads();
+  }
+  carry = T;
+  for (int c0 = (T - 1) / DOC_THREADS * DOC_THREADS; c0 >= 0; c0 -= DOC_THREADS) {
+    const int t = c0 + tid;
+    const int v = t < T && ids[t] == sep ? t + 1 : T;  // a separator at t: t + 1 starts a document (or is T)
+    doc_scan<false>(s, tid, v);
+    if (t < T) doc_end[t] = min(s[0][tid], carry);
+    carry = min(carry, s[0][0]);
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 extern "C" {
 
 int dtc_version() { return 1; }
+
+// ids int32 [rows, T] (what dtc_embed_fwd reads) -> doc_start, doc_end int32 [rows, T]
+int dtc_doc_bounds(const int* ids, int* doc_start, int* doc_end, int rows, int T, int sep, hipStream_t st) {
+  if (rows < 1 || T < 1) return 3014;  // (a code of its own in this file)
+  hipLaunchKernelGGL(doc_bounds_kernel, dim3(rows), dim3(DOC_THREADS), 0, st, ids, doc_start, doc_end, T, sep);
+  DTC_CHECK_LAUNCH();
+  return 0;
+}
 
 int dtc_embed_fwd(const int* ids, const float* wte, const float* wpe, float* h, int B, int T, int D, int V, float p,
                   long seed, const int64_t* step, long row0, hipStream_t st) {

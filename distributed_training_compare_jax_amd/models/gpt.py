@@ -406,7 +406,7 @@ class GPTStage:
         if y1q is None:
             y1q = MX.quant_mxfp8(y1)
         qkv = MX.linear_mxfp8(y1q, f.wmx(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=act)
-        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local)
+        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"))
         o = o.view(batch * T, -1)
         oq = MX.quant_mxfp8(o)
         if _ADD_LN:  # residual add in the LayerNorm pass, as block_forward
@@ -448,7 +448,7 @@ class GPTStage:
             qkv = F8.linear_fp8(F8.quant_e4m3(y1), f.w8(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=self.act_dtype)
         else:
             qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
-        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local)
+        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"))
         o = o.view(batch * T, -1)
         oq = F8.quant_e4m3(o) if fp8 else None
         if self._fuse_fwd:
@@ -552,7 +552,7 @@ class GPTStage:
             do = G.linear_backward(dx2_c, f.w(p + "out.w"), o, f.g(p + "out.w"), beta, red=red,
                                    out_dtype=self.act_dtype, pair=False)
         dqkv = A.attn_bwd(qkv.view(batch, T, -1), o.view(batch, T, -1), lse, do.view(batch, T, -1),
-                          self.heads_local).view(batch * T, -1)
+                          self.heads_local, doc=ctx.get("doc")).view(batch * T, -1)
         wtq = f.wt(p + "qkv.w")
         if self._fuse_bwd and wtq is not None:
             bg = self._prev_fc2b(l)
@@ -596,7 +596,7 @@ class GPTStage:
         y1l, mu1, rs1 = LN.layernorm_fwd(x, f.p(p + "ln1.g"), f.p(p + "ln1.b"), self.eps, self.act_dtype)
         y1 = tp.all_gather_rows(y1l)
         qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
-        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local)
+        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"))
         o = o.view(rows, -1)
         x2 = self._row_parallel_sp(o, p + "out.w", resid=x, bias=f.p(p + "out.b"))
         y2l, mu2, rs2 = LN.layernorm_fwd(x2, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, self.act_dtype)
@@ -644,7 +644,7 @@ class GPTStage:
             do = G.linear_backward(g2, f.w(p + "out.w"), o, f.g(p + "out.w"), beta, red=red,
                                    out_dtype=self.act_dtype, pair=False)
         dqkv = A.attn_bwd(qkv.view(batch, T, -1), o.view(batch, T, -1), lse, do.view(batch, T, -1),
-                          self.heads_local).view(rows, -1)
+                          self.heads_local, doc=ctx.get("doc")).view(rows, -1)
         dy1 = self._tp_rs(self._dgrad_wgrad(dqkv, p + "qkv", y1, beta, red, pair=True))
         out = self._ln_bwd(dy1, x, p + "ln1", mu1, rs1, dx2, beta, bias_grad=self._prev_fc2b(l))
         if dx_hook is not None:

@@ -54,18 +54,23 @@ class _FakeQuantLinear(torch.autograd.Function):
 
 def oracle_loss(cfg: ModelConfig, params: dict, ids: torch.Tensor, labels: torch.Tensor, seed: int, step: int,
                 row0: int = 0, fake_quant: bool = False, quant_bf16_inputs: bool = False,
-                quant_inputs: list = None) -> torch.Tensor:
+                quant_inputs: list = None, doc_mask_token: int = -1) -> torch.Tensor:
     """Mean cross-entropy of :func:`oracle_logits` (same arguments) against ``labels``."""
-    logits = oracle_logits(cfg, params, ids, seed, step, row0, fake_quant, quant_bf16_inputs, quant_inputs)
+    logits = oracle_logits(cfg, params, ids, seed, step, row0, fake_quant, quant_bf16_inputs, quant_inputs,
+                           doc_mask_token)
     V = cfg.vocab_size
     return F.cross_entropy(logits.reshape(-1, V), labels.reshape(-1).long())
 
 
 def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, step: int,
                   row0: int = 0, fake_quant: bool = False, quant_bf16_inputs: bool = False,
-                  quant_inputs: list = None) -> torch.Tensor:
+                  quant_inputs: list = None, doc_mask_token: int = -1) -> torch.Tensor:
     """Logits ``[B, T, vocab_size]``.  params: name → fp32 tensor (full shapes, [out,in] Dense layout),
     requires_grad allowed.
+
+    ``doc_mask_token`` >= 0 (``TrainConfig.doc_mask_token``): attention stops at document boundaries -- position
+    ``t`` starts a document iff ``t == 0`` or ``ids[b, t-1]`` is that token, and a query sees only the keys of its own
+    document up to itself.
 
     ``fake_quant`` (default off): the four layer GEMMs of every block (qkv, out_proj, fc1, fc2) run as
     :class:`_FakeQuantLinear`, the statement of ``TrainConfig.fwd_gemm_dtype: fp8``; the lm_head stays as it is.
@@ -90,6 +95,13 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
         h = torch.where(keep, h / (1 - cfg.dropout), torch.zeros_like(h))
     mask = torch.tril(torch.ones(T, T, device=h.device))
     add_mask = torch.where(mask == 1, 0.0, -1e9)  # GPTModel.py:50-51
+    if doc_mask_token >= 0:  # [B, 1, T, T]: the same additive form, keys before the query's document masked too
+        started = torch.ones(B, T, dtype=torch.bool, device=h.device)
+        started[:, 1:] = ids[:, :-1] == doc_mask_token
+        pos = torch.arange(T, device=h.device)
+        doc_start = torch.cummax(torch.where(started, pos.expand(B, T), torch.full((B, T), -1, device=h.device)), 1).values
+        see = (pos[None, None, :] >= doc_start[:, :, None]) & (mask == 1)[None]
+        add_mask = torch.where(see, 0.0, -1e9)[:, None]
     for l in range(cfg.n_layers):
         p = lambda n: params[f"h.{l}.{n}"]  # noqa: E731
         r = h

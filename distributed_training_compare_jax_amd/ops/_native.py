@@ -169,6 +169,10 @@ def _declare(lib):
         "dtc_attn_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, l, vp], i),
         "dtc_attn_bwd_workspace_bytes": ([i, i, i, i], l),
         "dtc_attn_plan": ([i, i, i, i, i, i, l, ctypes.POINTER(c_int)], i),
+        "dtc_attn_fwd_doc": ([vp, vp, vp, i, i, i, i, i, f, vp, vp, vp], i),
+        "dtc_attn_bwd_doc": ([vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, l, vp, vp, vp], i),
+        "dtc_attn_plan_doc": ([i, i, i, i, i, i, l, ctypes.POINTER(c_int)], i),
+        "dtc_doc_bounds": ([vp, vp, vp, i, i, i, vp], i),
         "dtc_attn_last_launch": ([ctypes.POINTER(c_int)], i),
         "dtc_attn_rec_ints": ([], i),
         "dtc_attn_kernel_count": ([], i),

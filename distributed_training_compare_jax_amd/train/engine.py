@@ -23,6 +23,7 @@ import torch.distributed as dist
 from ..config.schema import ModelConfig, OptimConfig, TrainConfig
 from ..models.gpt import GPTStage, StageLayout
 from ..models.params import stage_param_specs
+from ..ops import attention as A
 from ..ops import embedding as E
 from ..ops import gemm as G
 from ..ops import optim as O
@@ -133,6 +134,25 @@ class Engine:
             if why:
                 raise ValueError(f"grad_accum={k_acc} cannot be combined with {why}")
         self.grad_accum = int(k_acc)
+        # doc_mask_token: attention that stops at document boundaries (ops/attention.py doc_bounds; the bounds are
+        # computed from each (micro)step's own ids inside the step program).  Tensor parallelism needs nothing: the
+        # bounds depend on the row alone and every TP rank holds the ids of all the rows its attention runs on, with
+        # and without sequence parallelism (self.ids is the whole local batch; sequence parallelism splits rows
+        # only between the attention calls).  What it does not cover is refused here, by name.
+        self.doc_token = int(train_cfg.doc_mask_token)
+        if self.doc_token >= 0:
+            why = None
+            hd = model_cfg.d_model // model_cfg.n_heads
+            if pp > 1:
+                why = (f"pp={pp} (pipeline parallelism: the later stages hold no ids; the follow-up ships the bounds "
+                       "with the stage message)")
+            elif dinfo.device.type == "cuda" and train_cfg.dtype == "fp32":
+                why = "dtype=fp32 on the GPU (the exact-fp32 attention kernels have no document mask; use bf16)"
+            elif dinfo.device.type == "cuda" and hd not in (64, 128):
+                why = (f"head_dim {hd} on the GPU (d_model {model_cfg.d_model} / n_heads {model_cfg.n_heads}): the "
+                       "document-masked kernels are the 32-row family, head_dim 64 or 128")
+            if why:
+                raise ValueError(f"doc_mask_token={self.doc_token} cannot be combined with {why}")
         # eval_every: the held-out evaluation (evaluate) -- what it does not cover is refused here, by name
         if train_cfg.eval_every > 0:
             if pp > 1:
@@ -780,6 +800,7 @@ class Engine:
             last = j == k - 1
             ctx: Dict = {}
             r = slice(j * mb, (j + 1) * mb)
+            self._doc_bounds_into(ctx, self.ids[r])  # the microstep's own rows
             h = st.embed_forward(self.ids[r], step, self.row0 + j * mb, ctx, want_keys=False)
             h = st.stage_forward(h, mb, ctx)
             st.head_forward(h, self.labels[r], 1.0 / (b * T), ctx, loss_out=self.loss, accumulate=j > 0)
@@ -801,6 +822,12 @@ class Engine:
             del ctx
         return out
 
+    def _doc_bounds_into(self, ctx: Dict, ids: torch.Tensor):
+        """``doc_mask_token`` >= 0: the document bounds of these rows (one launch, inside the step program, from its
+        static ids) as ``ctx["doc"]``, where the stage's attention calls look for them.  Off: nothing."""
+        if self.doc_token >= 0:
+            ctx["doc"] = A.doc_bounds(ids, self.doc_token)
+
     def _accum_dx(self, j: int, dx: torch.Tensor, dx_c: Optional[torch.Tensor] = None):
         """Microstep j's embedding-output gradient into its rows of the full-batch buffer (``grad_accum``)."""
         n = self.mb_rows * self.T
@@ -820,6 +847,7 @@ class Engine:
         ctx: Dict = {}
         step = self.opt.step_t
         hk = self.keys if self.host_keys else None
+        self._doc_bounds_into(ctx, self.ids)
         h = st.embed_forward(self.ids, step, self.row0, ctx, want_keys=not self.embed_gather,
                              keys=None if self.embed_gather else hk)
         gathered = None
@@ -1074,6 +1102,7 @@ class Engine:
             for j in range(k):
                 r = slice(j * mb, (j + 1) * mb)
                 ctx: Dict = {}
+                self._doc_bounds_into(ctx, self.eval_ids[r])  # evaluation is judged under the mask it trains with
                 h = st.embed_forward(self.eval_ids[r], self.opt.step_t, self.row0 + j * mb, ctx, want_keys=False,
                                      dropout=0.0)
                 h = st.stage_forward(h, mb, ctx, keep=False)

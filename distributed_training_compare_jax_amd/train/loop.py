@@ -165,6 +165,7 @@ def train(train_config: TrainConfig, model_config: ModelConfig, opt_config: Opti
                   world_size=dinfo.world,
                   # one optimizer update per step over the global batch, run as grad_accum microbatches per rank
                   grad_accum=eng.grad_accum, microbatch_rows=eng.mb_rows,
+                  doc_mask_token=train_config.doc_mask_token,  # -1: plain causal attention over the whole row
                   lr_schedule=opt_config.lr_schedule)
     result["tflops_per_gpu"] = result["tflops"] / max(1, dinfo.world)
     if opt_config.param_groups:

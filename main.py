@@ -89,11 +89,15 @@ def _spawn_target(args):
 @click.option("--eval_every", type=int, default=None,
               help="held-out evaluation every N optimizer updates and after the last one (0 = off)")
 @click.option("--eval_batches", type=int, default=None, help="held-out batches per evaluation (default 8)")
+@click.option("--doc_mask_token", type=int, default=None,
+              help="separator (end-of-text) token id: attention stops at document boundaries (-1 = off)")
 @click.option("--set", "sets", multiple=True, metavar="KEY=VALUE",
               help="any other TrainConfig field, e.g. --set tp_comm=p2p --set pp_schedule=1f1b")
 def main(train_config_path: str, model_config_path: str, optim_config_path: str, nproc, steps, device, log_every,
-         warmup_steps, output_dir, profile, dtype, eval_every, eval_batches, sets):
+         warmup_steps, output_dir, profile, dtype, eval_every, eval_batches, doc_mask_token, sets):
     overrides = _parse_sets(sets)
+    if doc_mask_token is not None:
+        overrides["doc_mask_token"] = doc_mask_token
     if eval_every is not None:
         overrides["eval_every"] = eval_every
     if eval_batches is not None:
