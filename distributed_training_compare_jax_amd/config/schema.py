@@ -81,6 +81,12 @@ are optional and default to the reference behaviour:
   stops at document boundaries (a document starts at position 0 and after every separator; positions stay absolute,
   the loss is unchanged), in training and in evaluation, with bounds computed inside the step program from each
   (micro)step's ids.  GPU: bf16 at head_dim 64 / 128, pp = 1; ``metrics.json`` records the value.
+* ``ModelConfig.n_kv_heads`` (default None = ``n_heads``, multi-head attention): grouped-query attention with that many
+  K/V heads, a divisor of ``n_heads`` (1 = multi-query).  The fused projection then has ``(n_heads + 2 n_kv_heads) *
+  head_dim`` rows (``models/params.py``), query head ``h`` reads K/V head ``h // (n_heads // n_kv_heads)``, and
+  :meth:`ModelConfig.num_params` / :meth:`ModelConfig.flops_per_token` follow.  GPU: bf16 at head_dim 64 / 128, without
+  ``doc_mask_token`` and with ``fwd_gemm_dtype: bf16``; tensor parallelism shards whole groups (``n_kv_heads % tp ==
+  0``).  A checkpoint records the value.
 """
 
 from __future__ import annotations
@@ -109,10 +115,26 @@ class ModelConfig:
     vocab_pad_multiple: int = 128
     layernorm_eps: float = 1e-6  # flax nn.LayerNorm default
     name: str = "gpt-ref-89M"
+    n_kv_heads: Optional[int] = None  # grouped-query attention: K/V heads, a divisor of n_heads (None: n_heads)
+
+    def __post_init__(self):
+        kv = self.n_kv_heads
+        if kv is not None and (isinstance(kv, bool) or not isinstance(kv, int) or kv < 1 or self.n_heads % kv):
+            raise ValueError(f"n_kv_heads={kv!r}: expected a divisor of n_heads={self.n_heads} (or None: multi-head)")
 
     @property
     def head_dim(self) -> int:
         return self.d_model // self.n_heads
+
+    @property
+    def kv_heads(self) -> int:
+        """K/V heads of the attention: ``n_kv_heads``, or ``n_heads`` (multi-head) when it is None."""
+        return self.n_heads if self.n_kv_heads is None else self.n_kv_heads
+
+    @property
+    def qkv_rows(self) -> int:
+        """Rows of the fused Q / K / V projection: ``(n_heads + 2 kv_heads) * head_dim`` (3 d_model when multi-head)."""
+        return (self.n_heads + 2 * self.kv_heads) * self.head_dim
 
     @property
     def padded_vocab(self) -> int:
@@ -122,7 +144,8 @@ class ModelConfig:
     def num_params(self) -> int:
         """Parameter count of the reference architecture (unpadded vocab)."""
         D, F, V, T, L = self.d_model, self.d_ff, self.vocab_size, self.max_seq_len, self.n_layers
-        per_layer = 4 * D * D + 4 * D + D * F + F + F * D + D + 4 * D
+        Q = self.qkv_rows  # 3 D when multi-head
+        per_layer = (Q + D) * D + (Q + D) + D * F + F + F * D + D + 4 * D
         return V * D + T * D + L * per_layer + 2 * D + D * V + V
 
     def flops_per_token(self, causal: bool = True) -> float:
@@ -130,7 +153,7 @@ class ModelConfig:
         work of the causal attention, (T + 1) / 2 keys per query on average; ``causal=False``: the full
         T x T count SURVEY §2.4 / BASELINE.md's 1.715 TFLOP/step estimate use."""
         D, F, V, T, L = self.d_model, self.d_ff, self.vocab_size, self.max_seq_len, self.n_layers
-        mm = L * (4 * D * D + 2 * D * F) + D * V
+        mm = L * ((self.qkv_rows + D) * D + 2 * D * F) + D * V  # attention itself does not shrink with n_kv_heads
         keys = (T + 1) / 2.0 if causal else float(T)
         attn = L * 2 * keys * D  # QK^T + PV multiply-adds per token
         return 6.0 * mm + 3.0 * 2.0 * attn

@@ -89,7 +89,13 @@ enum Path {
   FWD_ROWS32_DOC,        // attn_fwd32_doc<64 / 128>
   BWD_ROWS32_DOC_128,    // delta, attn_bwd_dkdv32_doc<128>, attn_bwd_dq32_doc<128>
   BWD_ROWS32_DOC_MERGED, // delta, attn_bwd_merged32_doc<64>
-  PATH_COUNT,
+  PATH_COUNT,  // the multi-head and doc paths end here: the tests of those calls pin this count and the tables' tails
+  // grouped-query attention (plan_attn_fwd_gqa / plan_attn_bwd_gqa), appended behind the count: the 32-row family
+  // with shared K/V heads
+  FWD_ROWS32_GQA = PATH_COUNT,  // attn_fwd32_gqa<64 / 128>
+  BWD_ROWS32_GQA_128,           // delta, attn_bwd_dkdv32_gqa<128>, attn_bwd_dq32_gqa<128>
+  BWD_ROWS32_GQA_MERGED,        // delta, attn_bwd_merged32_gqa<64>
+  PATH_END,
 };
 
 // One id per instantiated kernel; KERNEL_NAMES[id] is the launch site's kernel expression without spaces and
@@ -114,7 +120,11 @@ enum Kernel {
   K_FWD32_DOC_64, K_FWD32_DOC_128,
   K_BWD_DQ32_DOC_128, K_BWD_DKDV32_DOC_128,
   K_BWD_MERGED32_DOC_64,
-  K_COUNT,
+  K_COUNT,  // as PATH_COUNT: KERNEL_NAMES ends here
+  K_FWD32_GQA_64 = K_COUNT, K_FWD32_GQA_128,  // the grouped-query kernels, named in GQA_KERNEL_NAMES[id - K_COUNT]
+  K_BWD_DQ32_GQA_128, K_BWD_DKDV32_GQA_128,
+  K_BWD_MERGED32_GQA_64,
+  K_END,
 };
 constexpr const char* KERNEL_NAMES[] = {
     "none",
@@ -138,6 +148,12 @@ constexpr const char* KERNEL_NAMES[] = {
     "attn_bwd_merged32_doc_kernel<64>",
 };
 static_assert(sizeof(KERNEL_NAMES) / sizeof(KERNEL_NAMES[0]) == K_COUNT, "one name per kernel id");
+constexpr const char* GQA_KERNEL_NAMES[] = {
+    "attn_fwd32_gqa_kernel<64>", "attn_fwd32_gqa_kernel<128>",
+    "attn_bwd_dq32_gqa_kernel<128>", "attn_bwd_dkdv32_gqa_kernel<128>",
+    "attn_bwd_merged32_gqa_kernel<64>",
+};
+static_assert(sizeof(GQA_KERNEL_NAMES) / sizeof(GQA_KERNEL_NAMES[0]) == K_END - K_COUNT, "one name per GQA kernel id");
 
 // ---- launch geometry the kernels and the plan share ------------------------------------------------------
 constexpr int RES_THREADS = 1024;
@@ -213,7 +229,8 @@ constexpr int MAX_LAUNCHES = 3;
 
 struct AttnPlan {
   int err = 0;  // the code the entry point returns instead of launching: 4001 head_dim, 4002 workspace,
-                // 4005 head_dim of a document-masked call (ERR_DOC_HEAD_DIM)
+                // 4005 head_dim of a document-masked call (ERR_DOC_HEAD_DIM), 4006 head_dim or head counts of a
+                // grouped-query call (ERR_GQA_SHAPE)
   int dir = DIR_NONE, path = PATH_NONE;
   int order = ORDER_NONE;  // the block order asked of attn_fwd5<64, 3>
   int order_n = 0;         // ORDER_BALANCED: blocks per XCD of the order; 0 = not one round, runs heavy-first
@@ -382,6 +399,52 @@ inline AttnPlan plan_attn_bwd_doc(int B, int T, int H, int HD, int flags, long w
     p.path = BWD_ROWS32_DOC_MERGED;
     p.add(K_DELTA_64, delta_grid, 256);
     p.add(K_BWD_MERGED32_DOC_64, 2 * g32, FW_THREADS);
+  }
+  return p;
+}
+
+// ---- grouped-query attention ---------------------------------------------------------------------------------
+// Hkv K/V heads for H = G Hkv query heads, packed rows [H | Hkv | Hkv] x head_dim (csrc/attention.hip, "grouped-query
+// attention").  The 32-row family at head_dim 64 and 128, whatever the flags and the knobs say, in the multi-head
+// twins' structure.  Forward and dQ: B H ceil(T / 128) blocks, logically heavy-first by query block then (b, h)
+// with h fastest, dealt so that the G heads of one K/V head are consecutive blocks of ONE XCD (attention.hip
+// gqa_block: every aligned run of 8 G block ids is read as its [G][8] grid transposed) and their K/V tiles hit in
+// that XCD's L2.  dK/dV: B Hkv ceil(T / 128) blocks, heavy-first by key block, each summing its group in registers.
+// head_dim 64 merges them into one launch, the dK/dV blocks first (gqa_dkdv_blocks of them), then the dQ blocks.
+// Any other head_dim, Hkv < 1 or H % Hkv != 0 is refused with ERR_GQA_SHAPE before the workspace is looked at.
+constexpr int ERR_GQA_SHAPE = 4006;
+
+constexpr long gqa_dkdv_blocks(int B, int T, int Hkv) { return (long)B * Hkv * cdiv(T, FW_QROWS); }
+inline bool gqa_shape_ok(int H, int Hkv, int HD) { return (HD == 64 || HD == 128) && Hkv >= 1 && H % Hkv == 0; }
+
+inline AttnPlan plan_attn_fwd_gqa(int B, int T, int H, int Hkv, int HD, int flags, int cus, const AttnKnobs& k) {
+  (void)flags; (void)cus; (void)k;
+  if (!gqa_shape_ok(H, Hkv, HD)) return refused(DIR_FWD, ERR_GQA_SHAPE);
+  AttnPlan p;
+  p.dir = DIR_FWD;
+  p.path = FWD_ROWS32_GQA;
+  p.add(HD == 128 ? K_FWD32_GQA_128 : K_FWD32_GQA_64, (long)B * H * cdiv(T, FW_QROWS), FW_THREADS);
+  return p;
+}
+
+inline AttnPlan plan_attn_bwd_gqa(int B, int T, int H, int Hkv, int HD, int flags, long ws_bytes, int cus,
+                                  const AttnKnobs& k) {
+  (void)flags; (void)cus; (void)k;
+  if (!gqa_shape_ok(H, Hkv, HD)) return refused(DIR_BWD, ERR_GQA_SHAPE);
+  if (ws_bytes < bwd_workspace_bytes(B, T, H)) return refused(DIR_BWD, 4002);
+  AttnPlan p;
+  p.dir = DIR_BWD;
+  const long gq = (long)B * H * cdiv(T, FW_QROWS), gk = gqa_dkdv_blocks(B, T, Hkv);
+  const long delta_grid = cdiv((long)B * H * T * (HD / 8), 256);
+  if (HD == 128) {
+    p.path = BWD_ROWS32_GQA_128;
+    p.add(K_DELTA_128, delta_grid, 256);
+    p.add(K_BWD_DKDV32_GQA_128, gk, FW_THREADS);
+    p.add(K_BWD_DQ32_GQA_128, gq, FW_THREADS);
+  } else {
+    p.path = BWD_ROWS32_GQA_MERGED;
+    p.add(K_DELTA_64, delta_grid, 256);
+    p.add(K_BWD_MERGED32_GQA_64, gk + gq, FW_THREADS);
   }
   return p;
 }

@@ -20,6 +20,9 @@ layer axis by ``nn.scan`` (``GPTModel.py:58-64``), then the final ``LayerNorm`` 
   input columns follow :func:`head_split`, which also covers a head count the TP degree does not
   divide (GPT-2 small's 12 heads on 8 ranks: 2,2,2,2,1,1,1,1 -- the reference cannot shard it at
   all).  Everything else (fc1/fc2, the padded vocab) splits evenly.
+* Grouped-query attention (``ModelConfig.n_kv_heads``): ``qkv.w`` has ``(H + 2 Hkv) * hd`` rows -- H query heads, Hkv
+  key heads, Hkv value heads -- and TP shards whole GROUPS: each slab is split evenly by its own heads, which keeps
+  every query head on the rank of its K/V head iff ``Hkv % tp == 0`` (anything else is refused by name).
 
 Flat-buffer order = the order backward produces gradients (head → layers L-1..0 →
 embeddings), so DP buckets are contiguous ranges that become ready in sequence.
@@ -50,6 +53,7 @@ class ParamSpec:
     mirror: bool               # has a bf16 compute copy (GEMM weight / bias / LN)
     valid_rows: int = -1       # for padded lm_head: rows >= valid_rows are zero
     heads: int = 0             # head-sharded (qkv_rows / head_cols): attention heads along the split dim
+    kv_heads: int = 0          # qkv_rows of grouped-query attention: K/V heads (0: as many as `heads`, three equal slabs)
     # (part, parts): the lm_head vocab split over the last `parts` PIPELINE stages (pp_head_split), applied
     # before the TP split: this stage holds rows [part * Vp / parts, (part + 1) * Vp / parts)
     vpart: Tuple[int, int] = (0, 1)
@@ -57,6 +61,7 @@ class ParamSpec:
 
 def layer_param_specs(cfg: ModelConfig, l: int) -> List[ParamSpec]:
     D, F, H = cfg.d_model, cfg.d_ff, cfg.n_heads
+    Q, kv = cfg.qkv_rows, (0 if cfg.kv_heads == H else cfg.kv_heads)
     p = f"h.{l}."
     # backward production order inside a block
     return [
@@ -68,8 +73,8 @@ def layer_param_specs(cfg: ModelConfig, l: int) -> List[ParamSpec]:
         ParamSpec(p + "ln2.b", (D,), "zeros", D, "rep", l, True),
         ParamSpec(p + "out.w", (D, D), "dense", D, "head_cols", l, True, heads=H),
         ParamSpec(p + "out.b", (D,), "zeros", D, "rep", l, True),
-        ParamSpec(p + "qkv.w", (3 * D, D), "dense", D, "qkv_rows", l, True, heads=H),
-        ParamSpec(p + "qkv.b", (3 * D,), "zeros", D, "qkv_rows", l, True, heads=H),
+        ParamSpec(p + "qkv.w", (Q, D), "dense", D, "qkv_rows", l, True, heads=H, kv_heads=kv),
+        ParamSpec(p + "qkv.b", (Q,), "zeros", D, "qkv_rows", l, True, heads=H, kv_heads=kv),
         ParamSpec(p + "ln1.g", (D,), "ones", D, "rep", l, True),
         ParamSpec(p + "ln1.b", (D,), "zeros", D, "rep", l, True),
     ]
@@ -164,6 +169,15 @@ def _head_range(spec: ParamSpec, width: int, tp_rank: int, tp_size: int) -> Tupl
     return h0 * hd, (h0 + n) * hd
 
 
+def gqa_slabs(spec: ParamSpec, tp_size: int) -> Tuple[int, int, int]:
+    """(head_dim, query heads, K/V heads) PER TP RANK of a grouped-query qkv tensor: whole groups on every rank."""
+    if spec.kv_heads % tp_size:
+        raise ValueError(f"{spec.name}: n_kv_heads {spec.kv_heads} is not a multiple of tp {tp_size}: tensor parallelism "
+                         "shards whole groups of query heads with their K/V head")
+    hd = spec.shape[0] // (spec.heads + 2 * spec.kv_heads)
+    return hd, spec.heads // tp_size, spec.kv_heads // tp_size
+
+
 def local_shape(spec: ParamSpec, tp_size: int, tp_rank: int = 0) -> Tuple[int, ...]:
     s = list(spec.shape)
     if spec.vpart[1] > 1:
@@ -171,7 +185,10 @@ def local_shape(spec: ParamSpec, tp_size: int, tp_rank: int = 0) -> Tuple[int, .
         s[0] //= spec.vpart[1]
     if tp_size == 1 or spec.tp == "rep":
         return tuple(s)
-    if spec.tp == "qkv_rows" and spec.heads:
+    if spec.tp == "qkv_rows" and spec.kv_heads:
+        hd, hq, hk = gqa_slabs(spec, tp_size)
+        s[0] = (hq + 2 * hk) * hd
+    elif spec.tp == "qkv_rows" and spec.heads:
         lo, hi = _head_range(spec, s[0] // 3, tp_rank, tp_size)
         s[0] = 3 * (hi - lo)
     elif spec.tp == "head_cols":
@@ -198,6 +215,10 @@ def shard(spec: ParamSpec, full: torch.Tensor, tp_rank: int, tp_size: int) -> to
     if spec.tp == "head_cols":
         lo, hi = _head_range(spec, full.shape[1], tp_rank, tp_size)
         return full[:, lo:hi].contiguous()
+    if spec.tp == "qkv_rows" and spec.kv_heads:  # [(H + 2 Hkv) hd, ...]: each slab's own heads, split evenly
+        hd, hq, hk = gqa_slabs(spec, tp_size)
+        slabs = full.split([spec.heads * hd, spec.kv_heads * hd, spec.kv_heads * hd], 0)
+        return torch.cat([t.chunk(tp_size, 0)[tp_rank] for t in slabs], 0).contiguous()
     if spec.tp == "qkv_rows":  # [3D, ...] -> per q/k/v slab, heads split
         three = full.reshape(3, full.shape[0] // 3, *full.shape[1:])
         if spec.heads:
@@ -215,6 +236,10 @@ def unshard(spec: ParamSpec, shards: List[torch.Tensor]) -> torch.Tensor:
         return torch.cat(shards, 0)
     if spec.tp in ("cols", "head_cols"):
         return torch.cat(shards, 1)
+    if spec.tp == "qkv_rows" and spec.kv_heads:
+        hd, hq, hk = gqa_slabs(spec, len(shards))
+        parts = [s.split([hq * hd, hk * hd, hk * hd], 0) for s in shards]
+        return torch.cat([torch.cat([p[i] for p in parts], 0) for i in range(3)], 0)
     if spec.tp == "qkv_rows":
         parts = [s.reshape(3, s.shape[0] // 3, *s.shape[1:]) for s in shards]
         return torch.cat(parts, 1).reshape(-1, *shards[0].shape[1:])

@@ -107,7 +107,11 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
         r = h
         x = F.layer_norm(h, (D,), p("ln1.g"), p("ln1.b"), eps)
         qkv = mm(x, p("qkv.w")) + p("qkv.b")
-        q, k, v = qkv.view(B, T, 3, H, hd).unbind(2)
+        # grouped-query attention (cfg.n_kv_heads): rows [H | Hkv | Hkv] x hd, every K/V head repeated for its group
+        Hkv = cfg.kv_heads
+        q, k, v = qkv.split([H * hd, Hkv * hd, Hkv * hd], -1)
+        q = q.view(B, T, H, hd)
+        k, v = (t.view(B, T, Hkv, hd).repeat_interleave(H // Hkv, 2) for t in (k, v))
         s = torch.einsum("bthd,bshd->bhts", q, k) * hd ** -0.5 + add_mask
         a = torch.softmax(s, -1)
         o = torch.einsum("bhts,bshd->bthd", a, v).reshape(B, T, D)

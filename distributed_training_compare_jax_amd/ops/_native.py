@@ -172,11 +172,16 @@ def _declare(lib):
         "dtc_attn_fwd_doc": ([vp, vp, vp, i, i, i, i, i, f, vp, vp, vp], i),
         "dtc_attn_bwd_doc": ([vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, l, vp, vp, vp], i),
         "dtc_attn_plan_doc": ([i, i, i, i, i, i, l, ctypes.POINTER(c_int)], i),
+        "dtc_attn_fwd_gqa": ([vp, vp, vp, i, i, i, i, i, i, f, vp], i),
+        "dtc_attn_bwd_gqa": ([vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, l, vp], i),
+        "dtc_attn_plan_gqa": ([i, i, i, i, i, i, i, l, ctypes.POINTER(c_int)], i),
         "dtc_doc_bounds": ([vp, vp, vp, i, i, i, vp], i),
         "dtc_attn_last_launch": ([ctypes.POINTER(c_int)], i),
         "dtc_attn_rec_ints": ([], i),
         "dtc_attn_kernel_count": ([], i),
         "dtc_attn_path_count": ([], i),
+        "dtc_attn_kernel_end": ([], i),
+        "dtc_attn_path_end": ([], i),
         "dtc_ce_combine": ([vp, i, i, l, l, vp, vp, vp, f, vp, i, vp], i),
         "dtc_ce_eval_finish": ([vp, l, l, vp, i, l, l, i, i, i, vp, vp, vp, vp, vp, vp], i),
         "dtc_row_argmax_f32": ([vp, l, i, i, vp, vp, vp], i),

@@ -25,6 +25,15 @@ Document-masked attention (packed sequences): :func:`doc_bounds` turns ``ids[B, 
 key ``k`` iff ``doc_start[b, q] <= k <= q``, equivalently ``k <= q < doc_end[b, k]``.  On the GPU that is the
 doc instantiations of the 32-row kernels at head_dim 64 and 128, bf16 (any other head_dim is refused with code
 4005, fp32 tensors raise ``NotImplementedError``); on the CPU a materialised boolean mask, any head_dim.
+
+Grouped-query attention: ``n_kv_heads = Hkv`` (a divisor of ``H``; 1 = multi-query) on ``attn_fwd`` / ``attn_bwd`` /
+``plan_*``.  The packed rows are then ``qkv[B, T, (H + 2 Hkv) hd]``: H query heads, Hkv key heads, Hkv value heads,
+query head ``h`` on K/V head ``h // (H // Hkv)``; ``dqkv`` has the same layout, ``o`` and ``lse`` keep theirs.
+``None`` or ``Hkv == H`` is the multi-head code path, unchanged.  On the GPU: the GQA instantiations of the 32-row
+kernels at head_dim 64 and 128, bf16 (``dtc_attn_fwd_gqa`` / ``dtc_attn_bwd_gqa``; another head_dim or ``H % Hkv != 0``
+is refused with code 4006, fp32 tensors and ``doc=`` raise ``NotImplementedError``); dK / dV of a K/V head are summed
+over its group in fp32 registers inside one block, so the result is deterministic.  On the CPU: repeated K/V heads,
+any head_dim.
 """
 
 from __future__ import annotations
@@ -72,6 +81,11 @@ KERNELS = ("none", "attn_delta_kernel<32>", "attn_delta_kernel<64>", "attn_delta
            "attn_bwd_dq32_kernel<128,true>", "attn_bwd_dkdv32_kernel<64>", "attn_bwd_dkdv32_kernel<128>",
            "attn_bwd_merged32_kernel<64>", "attn_fwd32_doc_kernel<64>", "attn_fwd32_doc_kernel<128>",
            "attn_bwd_dq32_doc_kernel<128>", "attn_bwd_dkdv32_doc_kernel<128>", "attn_bwd_merged32_doc_kernel<64>")
+# the grouped-query paths and kernels: the header appends their ids behind PATH_COUNT / K_COUNT (the tables above end
+# where the multi-head and doc tests pin them), so a recorded id indexes PATHS + GQA_PATHS / KERNELS + GQA_KERNELS
+GQA_PATHS = ("fwd_rows32_gqa", "bwd_rows32_gqa_128", "bwd_rows32_gqa_merged")
+GQA_KERNELS = ("attn_fwd32_gqa_kernel<64>", "attn_fwd32_gqa_kernel<128>", "attn_bwd_dq32_gqa_kernel<128>",
+               "attn_bwd_dkdv32_gqa_kernel<128>", "attn_bwd_merged32_gqa_kernel<64>")
 REC_INTS = 17
 _ENUMS_CHECKED = [False]
 
@@ -92,8 +106,8 @@ class AttnLaunch(collections.namedtuple("AttnLaunch", "direction path order orde
 
 def _record(out) -> AttnLaunch:
     v = list(out)
-    launches = tuple(Launch(KERNELS[v[5 + 4 * i]], *v[6 + 4 * i:9 + 4 * i]) for i in range(v[4]))
-    return AttnLaunch(DIRECTIONS[v[0]], PATHS[v[1]], ORDERS[v[2]], v[3], launches)
+    launches = tuple(Launch((KERNELS + GQA_KERNELS)[v[5 + 4 * i]], *v[6 + 4 * i:9 + 4 * i]) for i in range(v[4]))
+    return AttnLaunch(DIRECTIONS[v[0]], (PATHS + GQA_PATHS)[v[1]], ORDERS[v[2]], v[3], launches)
 
 
 def _rec_buffer():
@@ -101,6 +115,7 @@ def _rec_buffer():
         L = N.lib()
         assert (L.dtc_attn_kernel_count(), L.dtc_attn_path_count(), L.dtc_attn_rec_ints()) == (
             len(KERNELS), len(PATHS), REC_INTS)
+        assert (L.dtc_attn_kernel_end(), L.dtc_attn_path_end()) == (len(KERNELS + GQA_KERNELS), len(PATHS + GQA_PATHS))
         _ENUMS_CHECKED[0] = True
     return (ctypes.c_int * REC_INTS)()
 
@@ -113,10 +128,23 @@ def last_launch() -> AttnLaunch:
     return _record(out)
 
 
-def plan_fwd(B: int, T: int, H: int, hd: int, flags: int = 0, doc: bool = False) -> AttnLaunch:
+def _gqa(n_heads: int, n_kv_heads, doc=None) -> bool:
+    """Whether a call with these head counts takes the grouped-query path (``None`` and ``H`` do not)."""
+    if n_kv_heads is None or n_kv_heads == n_heads:
+        return False
+    if doc is not None and doc is not False:
+        raise NotImplementedError("grouped-query attention (n_kv_heads < n_heads) has no document-masked kernels")
+    return True
+
+
+def plan_fwd(B: int, T: int, H: int, hd: int, flags: int = 0, doc: bool = False, n_kv_heads=None) -> AttnLaunch:
     """The record a bf16 ``attn_fwd`` of this shape and ``flags`` would leave, without launching anything
-    (``doc``: of a document-masked call).  A shape the call would refuse raises as the call does."""
+    (``doc``: of a document-masked call; ``n_kv_heads``: of a grouped-query call).  A shape the call would refuse
+    raises as the call does."""
     out = _rec_buffer()
+    if _gqa(H, n_kv_heads, doc):
+        N.check(N.lib().dtc_attn_plan_gqa(1, B, T, H, n_kv_heads, hd, int(flags), 0, out), "dtc_attn_plan_gqa")
+        return _record(out)
     if doc:
         N.check(N.lib().dtc_attn_plan_doc(1, B, T, H, hd, int(flags), 0, out), "dtc_attn_plan_doc")
         return _record(out)
@@ -125,12 +153,15 @@ def plan_fwd(B: int, T: int, H: int, hd: int, flags: int = 0, doc: bool = False)
 
 
 def plan_bwd(B: int, T: int, H: int, hd: int, flags: int = 0, ws_bytes: int | None = None,
-             doc: bool = False) -> AttnLaunch:
+             doc: bool = False, n_kv_heads=None) -> AttnLaunch:
     """As :func:`plan_fwd`, for ``attn_bwd`` (``ws_bytes``: the workspace the call would hold; default: what it
     needs)."""
     L = N.lib()
     ws_bytes = int(L.dtc_attn_bwd_workspace_bytes(B, T, H, hd)) if ws_bytes is None else ws_bytes
     out = _rec_buffer()
+    if _gqa(H, n_kv_heads, doc):
+        N.check(L.dtc_attn_plan_gqa(2, B, T, H, n_kv_heads, hd, int(flags), ws_bytes, out), "dtc_attn_plan_gqa")
+        return _record(out)
     if doc:
         N.check(L.dtc_attn_plan_doc(2, B, T, H, hd, int(flags), ws_bytes, out), "dtc_attn_plan_doc")
         return _record(out)
@@ -177,7 +208,23 @@ def _check_doc(doc, qkv):
                                   "doc kernels)")
 
 
-def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags: int = 0, doc=None):
+def _split_heads(qkv: torch.Tensor, n_heads: int, n_kv_heads: int):
+    """Packed rows -> (hd, q [B,T,H,hd], k, v [B,T,Hkv,hd]) in fp32 (the CPU branch)."""
+    B, T, C = qkv.shape
+    hd = C // (n_heads + 2 * n_kv_heads)
+    assert n_heads % n_kv_heads == 0 and C == (n_heads + 2 * n_kv_heads) * hd, (C, n_heads, n_kv_heads)
+    q, k, v = qkv.float().split([n_heads * hd, n_kv_heads * hd, n_kv_heads * hd], -1)
+    return hd, q.view(B, T, n_heads, hd), k.view(B, T, n_kv_heads, hd), v.view(B, T, n_kv_heads, hd)
+
+
+def _check_gqa(qkv):
+    if qkv.dtype != torch.bfloat16:
+        raise NotImplementedError("grouped-query attention on the GPU is bf16 only (csrc/attention_f32.hip has no "
+                                  "GQA kernels)")
+
+
+def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags: int = 0, doc=None,
+             n_kv_heads: int | None = None):
     """qkv [B,T,3*H*hd] → (o [B,T,H*hd], lse [B,H,T] fp32, natural-log units).  ``flags``: a :class:`FwdFlags`
     (or its integer), A/B switches of the bf16 kernels.  At head_dim 32 only ``PLAIN_WAVES`` means anything, and
     only on the resident kernel.  At head_dim 64 the default is the round-5 pipeline at 3 waves per SIMD with
@@ -185,12 +232,16 @@ def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags:
     heavy-first order, ``WPS2`` runs it at 2 waves per SIMD, ``ROUND4`` picks the round-4 32-row kernel and
     ``CHUNK16`` the 16-row chunk kernel (``CHUNK16`` beats ``ROUND4`` beats ``WPS2``).  head_dim 128 has one
     forward kernel and ignores ``flags``.  ``doc = (doc_start, doc_end)`` (:func:`doc_bounds`): attention stops at
-    document boundaries; bf16 at head_dim 64 / 128 on the GPU, whatever ``flags`` say."""
+    document boundaries; bf16 at head_dim 64 / 128 on the GPU, whatever ``flags`` say.  ``n_kv_heads`` (a divisor
+    of ``n_heads``, smaller than it): grouped-query attention on ``qkv [B,T,(H+2*Hkv)*hd]`` (module docstring)."""
     B, T, C3 = qkv.shape
-    hd = C3 // (3 * n_heads)
+    gqa = _gqa(n_heads, n_kv_heads, doc if not N.library_path(qkv) else None)
+    hkv = n_kv_heads if gqa else n_heads
+    hd = C3 // (n_heads + 2 * hkv)
     scale = scale if scale is not None else hd ** -0.5
     if N.library_path(qkv):
-        q, k, v = qkv.float().view(B, T, 3, n_heads, hd).unbind(2)
+        _, q, k, v = _split_heads(qkv, n_heads, hkv)
+        k, v = (t.repeat_interleave(n_heads // hkv, 2) for t in (k, v))
         s = torch.einsum("bthd,bshd->bhts", q, k) * scale
         mask = torch.ones(T, T, dtype=torch.bool, device=qkv.device).tril()
         if doc is not None:
@@ -201,6 +252,13 @@ def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags:
         o = torch.einsum("bhts,bshd->bthd", p, v).reshape(B, T, n_heads * hd)
         return o.to(qkv.dtype), lse
     assert qkv.dtype in (torch.bfloat16, torch.float32) and qkv.is_contiguous()
+    if gqa:
+        _check_gqa(qkv)
+        o = torch.empty(B, T, n_heads * hd, dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(B, n_heads, T, dtype=torch.float32, device=qkv.device)
+        N.check(N.lib().dtc_attn_fwd_gqa(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), B, T, n_heads, n_kv_heads, hd,
+                                         int(flags), scale, N.stream_ptr(qkv.device)), "dtc_attn_fwd_gqa")
+        return o, lse
     if doc is not None:
         _check_doc(doc, qkv)
         o = torch.empty(B, T, n_heads * hd, dtype=qkv.dtype, device=qkv.device)
@@ -223,18 +281,23 @@ def attn_fwd(qkv: torch.Tensor, n_heads: int, scale: float | None = None, flags:
 
 
 def attn_bwd(qkv: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor, n_heads: int,
-             scale: float | None = None, flags: int = 0, doc=None) -> torch.Tensor:
+             scale: float | None = None, flags: int = 0, doc=None, n_kv_heads: int | None = None) -> torch.Tensor:
     """Returns dqkv [B,T,3*H*hd] (same dtype as qkv).  ``flags``: a :class:`BwdFlags` (or its integer), A/B
     switches of the bf16 kernels.  ``TWO_ROUND`` forces the two-round resident kernels instead of the fused
     single-round one (head_dim 32, resident shapes only); at head_dim 64 ``CHUNK16`` picks the 16-row chunk pair
     and ``FORCE_MERGED`` the delta pass + merged launch even with ``DTC_ATTN_BWD_MERGED=0`` (``CHUNK16`` wins).
     head_dim 128 has one backward path (delta pass, dK/dV kernel, dQ kernel) and ignores ``flags``.  ``doc``: as
-    :func:`attn_fwd` (the same bounds the forward ran with); the doc kernels mirror those two paths."""
+    :func:`attn_fwd` (the same bounds the forward ran with); the doc kernels mirror those two paths.
+    ``n_kv_heads``: as :func:`attn_fwd`; dK / dV of a K/V head are the sums over its group of query heads."""
     B, T, C3 = qkv.shape
-    hd = C3 // (3 * n_heads)
+    gqa = _gqa(n_heads, n_kv_heads, doc if not N.library_path(qkv) else None)
+    hkv = n_kv_heads if gqa else n_heads
+    hd = C3 // (n_heads + 2 * hkv)
     scale = scale if scale is not None else hd ** -0.5
     if N.library_path(qkv):
-        q, k, v = qkv.float().view(B, T, 3, n_heads, hd).unbind(2)
+        G = n_heads // hkv
+        _, q, k, v = _split_heads(qkv, n_heads, hkv)
+        k, v = (t.repeat_interleave(G, 2) for t in (k, v))
         dof = do.float().view(B, T, n_heads, hd)
         s = torch.einsum("bthd,bshd->bhts", q, k) * scale
         mask = torch.ones(T, T, dtype=torch.bool, device=qkv.device).tril()
@@ -248,10 +311,18 @@ def attn_bwd(qkv: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, do: torch.Te
         ds = p * (dp - delta[..., None]) * scale
         dq = torch.einsum("bhts,bshd->bthd", ds, k)
         dk = torch.einsum("bhts,bthd->bshd", ds, q)
-        return torch.stack([dq, dk, dv], 2).reshape(B, T, C3).to(qkv.dtype)
+        dk, dv = (t.view(B, T, hkv, G, hd).sum(3) for t in (dk, dv))  # the group's sum (G = 1: the head itself)
+        return torch.cat([t.reshape(B, T, -1) for t in (dq, dk, dv)], -1).to(qkv.dtype)
     assert do.is_contiguous() and o.is_contiguous()
     dqkv = torch.empty_like(qkv)
     L = N.lib()
+    if gqa:
+        _check_gqa(qkv)
+        ws = _workspace(qkv.device, int(L.dtc_attn_bwd_workspace_bytes(B, T, n_heads, hd)))
+        N.check(L.dtc_attn_bwd_gqa(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(), dqkv.data_ptr(),
+                                   int(flags), B, T, n_heads, n_kv_heads, hd, scale, ws.data_ptr(),
+                                   ws.numel() * ws.element_size(), N.stream_ptr(qkv.device)), "dtc_attn_bwd_gqa")
+        return dqkv
     if doc is not None:
         _check_doc(doc, qkv)
         ws = _workspace(qkv.device, int(L.dtc_attn_bwd_workspace_bytes(B, T, n_heads, hd)))

@@ -153,6 +153,25 @@ class Engine:
                        "document-masked kernels are the 32-row family, head_dim 64 or 128")
             if why:
                 raise ValueError(f"doc_mask_token={self.doc_token} cannot be combined with {why}")
+        # n_kv_heads: grouped-query attention (ops/attention.py).  Data, tensor (whole groups per rank) and pipeline
+        # parallelism need nothing of their own -- pipeline stages exchange activations only, never K or V.  What the
+        # GQA kernels do not cover is refused here, by name.
+        if model_cfg.kv_heads != model_cfg.n_heads:
+            why = None
+            hd = model_cfg.d_model // model_cfg.n_heads
+            if model_cfg.kv_heads % tp:
+                why = f"tp={tp} (tensor parallelism shards whole groups: n_kv_heads must be a multiple of tp)"
+            elif self.doc_token >= 0:
+                why = f"doc_mask_token={self.doc_token} (there are no document-masked GQA kernels)"
+            elif train_cfg.fwd_gemm_dtype != "bf16":
+                why = f"fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the FP8 / MXFP8 forwards have not been run with it)"
+            elif dinfo.device.type == "cuda" and train_cfg.dtype == "fp32":
+                why = "dtype=fp32 on the GPU (the exact-fp32 attention kernels have no GQA variant; use bf16)"
+            elif dinfo.device.type == "cuda" and hd not in (64, 128):
+                why = (f"head_dim {hd} on the GPU (d_model {model_cfg.d_model} / n_heads {model_cfg.n_heads}): the GQA "
+                       "kernels are the 32-row family, head_dim 64 or 128")
+            if why:
+                raise ValueError(f"n_kv_heads={model_cfg.kv_heads} cannot be combined with {why}")
         # eval_every: the held-out evaluation (evaluate) -- what it does not cover is refused here, by name
         if train_cfg.eval_every > 0:
             if pp > 1:

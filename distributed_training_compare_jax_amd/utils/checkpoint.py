@@ -50,7 +50,8 @@ def save(eng, output_dir: str, step: int):
                 zero_stage=int(getattr(eng, "zero", False)), **_zero_meta(eng),
                 lr_schedule=eng.ocfg.schedule_key(), param_groups=eng.ocfg.groups_key(),
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
-                vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab))
+                vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab),
+                n_kv_heads=int(eng.mcfg.kv_heads))
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
         json.dump(meta, fh)
 
@@ -130,6 +131,11 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
     if groups_ck != groups_now:
         raise ValueError(f"checkpoint was written under param_groups {groups_ck!r}, this run has {groups_now!r} "
                          "(patterns|wd|lr_scale per group): resume with the groups that wrote it")
+    # the K/V heads set the rows of every qkv tensor (checkpoints from before the field: multi-head)
+    kv_ck, kv_now = int(m0.get("n_kv_heads", eng.mcfg.n_heads)), int(eng.mcfg.kv_heads)
+    if kv_ck != kv_now:
+        raise ValueError(f"checkpoint was written with n_kv_heads={kv_ck}, this run has n_kv_heads={kv_now}: the fused "
+                         "qkv projection has other rows")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
     for r, m in metas.items():
