@@ -87,6 +87,12 @@ are optional and default to the reference behaviour:
   :meth:`ModelConfig.num_params` / :meth:`ModelConfig.flops_per_token` follow.  GPU: bf16 at head_dim 64 / 128, without
   ``doc_mask_token`` and with ``fwd_gemm_dtype: bf16``; tensor parallelism shards whole groups (``n_kv_heads % tp ==
   0``).  A checkpoint records the value.
+* ``ModelConfig.pos_emb`` (``learned`` | ``rope``, default ``learned``) / ``rope_theta`` (default 10000): ``rope`` drops
+  the learned position table (no ``wpe`` parameter, :meth:`ModelConfig.num_params` follows) and rotates the Q and K heads
+  of every layer by their position instead (rotate-half pairing, angles ``t * rope_theta**(-2i/head_dim)``; ``ops/rope.py``,
+  ``csrc/rope.hip``: one in-place pass over ``qkv`` after its GEMM, the transposed one over ``dqkv`` after the attention
+  backward).  Only position differences reach the scores, so ``doc_mask_token`` needs no per-document reset.  ``head_dim``
+  must be even (GPU: 32, 64 or 128); every dtype, layout and forward GEMM mode.  A checkpoint records both values.
 """
 
 from __future__ import annotations
@@ -116,8 +122,20 @@ class ModelConfig:
     layernorm_eps: float = 1e-6  # flax nn.LayerNorm default
     name: str = "gpt-ref-89M"
     n_kv_heads: Optional[int] = None  # grouped-query attention: K/V heads, a divisor of n_heads (None: n_heads)
+    pos_emb: str = "learned"  # learned (the wpe table) | rope (rotary embeddings on Q and K, no wpe: ops/rope.py)
+    rope_theta: float = 10000.0  # rope: the angles are t * rope_theta**(-2i/head_dim)
 
     def __post_init__(self):
+        import math
+
+        if self.pos_emb not in ("learned", "rope"):
+            raise ValueError(f"pos_emb={self.pos_emb!r}: expected 'learned' or 'rope'")
+        th = self.rope_theta
+        if isinstance(th, bool) or not isinstance(th, (int, float)) or not math.isfinite(th) or th <= 0:
+            raise ValueError(f"rope_theta={th!r}: expected a finite number > 0")
+        if self.pos_emb == "rope" and self.head_dim % 2:
+            raise ValueError(f"pos_emb='rope' needs an even head_dim (d_model {self.d_model} / n_heads {self.n_heads} "
+                             f"= {self.head_dim}): the rotation pairs element i with i + head_dim / 2")
         kv = self.n_kv_heads
         if kv is not None and (isinstance(kv, bool) or not isinstance(kv, int) or kv < 1 or self.n_heads % kv):
             raise ValueError(f"n_kv_heads={kv!r}: expected a divisor of n_heads={self.n_heads} (or None: multi-head)")
@@ -146,7 +164,8 @@ class ModelConfig:
         D, F, V, T, L = self.d_model, self.d_ff, self.vocab_size, self.max_seq_len, self.n_layers
         Q = self.qkv_rows  # 3 D when multi-head
         per_layer = (Q + D) * D + (Q + D) + D * F + F + F * D + D + 4 * D
-        return V * D + T * D + L * per_layer + 2 * D + D * V + V
+        pos = T * D if self.pos_emb == "learned" else 0  # rope has no position table
+        return V * D + pos + L * per_layer + 2 * D + D * V + V
 
     def flops_per_token(self, causal: bool = True) -> float:
         """Matmul FLOPs per token, fwd+bwd: 6 * N_matmul + attention.  ``causal`` (default): the useful

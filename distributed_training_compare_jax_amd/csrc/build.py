@@ -35,7 +35,9 @@ FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-munsafe-fp-at
 DEBUG_FLAGS = ["-O1", "-g", "-DDTC_DEBUG", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
                "-Wno-unused-result"]
 DEBUG_OUT = os.path.join(PKG, "_dtc_kernels_debug.so")
-FILE_FLAGS = {}  # per-file extra hipcc options (basename -> list)
+# per-file extra hipcc options (basename -> list).  rope.hip: plain fp32 multiplies and FMAs for the rotation, no
+# packed-fp32 forms
+FILE_FLAGS = {"rope.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 STATUS = {"kernels": None, "host": None}  # "compiled" | "reused" after build()
 
 

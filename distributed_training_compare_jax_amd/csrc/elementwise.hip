@@ -51,7 +51,9 @@ __global__ void __launch_bounds__(256) embed_fwd_kernel(const int* __restrict__ 
 #pragma unroll
     for (int k = 0; k < VPL; ++k) {
       const int c = c0 + k * 64 + lane;
-      if (c < D4) v[k] = *(const f32x4*)(wte + (long)id * D + 4 * c) + *(const f32x4*)(wpe + (long)t * D + 4 * c);
+      if (c >= D4) continue;
+      if (wpe) v[k] = *(const f32x4*)(wte + (long)id * D + 4 * c) + *(const f32x4*)(wpe + (long)t * D + 4 * c);
+      else v[k] = *(const f32x4*)(wte + (long)id * D + 4 * c);  // no position table (pos_emb: rope), kernel-uniform
     }
 #pragma unroll
     for (int k = 0; k < VPL; ++k) {
@@ -1064,8 +1066,9 @@ int dtc_embed_sort(const int* ids, int n, int V, uint32_t* keys, hipStream_t st)
 // P = n*D fp32 scratch.  Bitwise deterministic.
 // sq (optional; accumulate == 0): dtc_embed_sq_slots(B, T, D) sum-of-squares partials of the final dwte / dwpe
 // values -- the gradient norm's share of the two tables without a pass over them (FusedAdamW fused partials)
-long dtc_embed_sq_slots(int B, int T, int D) {
-  const long dblk = (D / 4 + 63) / 64, nwpe = ((long)T * (D / 4) + 63) / 64;
+// has_wpe = 0: the call has no position table (dwpe null): no dwpe blocks, no dwpe slots
+long dtc_embed_sq_slots(int B, int T, int D, int has_wpe) {
+  const long dblk = (D / 4 + 63) / 64, nwpe = has_wpe ? ((long)T * (D / 4) + 63) / 64 : 0;
   return (long)B * T * dblk + nwpe;
 }
 
@@ -1088,7 +1091,7 @@ int dtc_embed_bwd(const uint32_t* keys, const float* dh, float* dwte, float* dwp
   const long n4 = accumulate ? 0 : (long)V * D / 4;
   const bool sparse = prev_keys && prev_valid;
   const long nzero = sparse ? n : (n4 + EB_ZCH - 1) / EB_ZCH;
-  const long nwpe = ((long)T * (D / 4) + 63) / 64;
+  const long nwpe = dwpe ? ((long)T * (D / 4) + 63) / 64 : 0;  // no position table: no dwpe blocks
   const long nblk = nzero + (long)npieces * dblk + nwpe;
   if (nblk > 0x7fffffffL) return 3004;
   hipLaunchKernelGGL(embed_bwd_stage1, dim3((unsigned)nblk), dim3(64), 0, st, keys, n, nb, piece, npieces, dblk, dh, P,

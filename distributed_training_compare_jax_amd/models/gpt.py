@@ -34,6 +34,7 @@ from ..ops import layernorm as LN
 from ..ops import fp8 as F8
 from ..ops import mxfp8 as MX
 from ..ops import ln_fused as LF
+from ..ops import rope as R
 from ..ops import xent as X
 from ..ops.reduce import GradReducer
 from .params import head_split
@@ -148,6 +149,10 @@ class GPTStage:
         # grouped-query attention: this rank's K/V heads (None: multi-head, the attention ops' unchanged path); TP holds
         # whole groups (models/params.py gqa_slabs refuses n_kv_heads % tp != 0)
         self.kv_heads_local = None if cfg.kv_heads == H else cfg.kv_heads // self.tp.size
+        # rotary embeddings (pos_emb: rope): the (cos, sin) table of this stage, a plain device tensor built once --
+        # not a parameter, not checkpoint state; None = learned positions (the wpe table)
+        self.rope_tab = (R.rope_table(cfg.max_seq_len, cfg.head_dim, cfg.rope_theta, dev)
+                         if cfg.pos_emb == "rope" else None)
         part, parts = layout.head_part
         self.v_local = cfg.padded_vocab // parts // self.tp.size
         self.v_start = part * (cfg.padded_vocab // parts) + self.tp.rank * self.v_local
@@ -327,23 +332,32 @@ class GPTStage:
         li = l - self.layout.layers[0]
         return 2 * L + 2 * (L - 1 - li) + k if backward else 2 * li + k
 
+    def _rope(self, qkv: torch.Tensor, batch: int, inverse: bool = False):
+        """pos_emb: rope -- rotate the local Q and K heads of ``qkv [batch * T, .]`` in place (``ops/rope.py``): the
+        forward right after the qkv GEMM (``ctx`` keeps the rotated tensor: the attention backward needs it), the
+        transposed rotation on ``dqkv`` right after the attention backward."""
+        if self.rope_tab is not None:
+            R.rope_(qkv.view(batch, qkv.shape[0] // batch, -1), self.rope_tab, self.heads_local,
+                    self.kv_heads_local or self.heads_local, inverse)
+
     # ------------------------------------------------------------------ embed
     def embed_forward(self, ids: torch.Tensor, step: torch.Tensor, row0: int, ctx: Dict,
                       want_keys: bool = True, keys: Optional[torch.Tensor] = None,
                       dropout: Optional[float] = None) -> torch.Tensor:
-        """ids int32 [b, T] → h fp32 [b*T, D]  (wte gather + wpe + dropout, GPTModel.py:30-38).
+        """ids int32 [b, T] → h fp32 [b*T, D]  (wte gather + wpe + dropout, GPTModel.py:30-38; no wpe under pos_emb: rope).
 
         ``keys``: the backward's sort keys, already computed on the host (``E.embed_sort_keys_host``);
         otherwise (``want_keys``) they are sorted on the device.  ``dropout``: the rate instead of the
         model's (evaluation: 0; ``step`` is then read by nothing)."""
         f = self.flat
+        wpe = f.p("wpe") if f.has("wpe") else None
         p_drop = self.cfg.dropout if dropout is None else float(dropout)
         if self.sp:  # this rank's sequences only (the backward gathers the output grads of all of them)
             bl = ids.shape[0] // self.tp.size
             r0 = self.tp.rank * bl
-            h = E.embed_fwd(ids[r0:r0 + bl], f.p("wte"), f.p("wpe"), p_drop, self.seed, step, row0 + r0)
+            h = E.embed_fwd(ids[r0:r0 + bl], f.p("wte"), wpe, p_drop, self.seed, step, row0 + r0)
         else:
-            h = E.embed_fwd(ids, f.p("wte"), f.p("wpe"), p_drop, self.seed, step, row0)
+            h = E.embed_fwd(ids, f.p("wte"), wpe, p_drop, self.seed, step, row0)
         if keys is not None:
             ctx["embed"] = (ids, row0, (keys, None))
         else:
@@ -376,7 +390,7 @@ class GPTStage:
         prev = self.emb_prev
         if prev is not None and (beta != 0.0 or gathered is not None or self.sp):
             raise RuntimeError("sparse wte zeroing needs one local embedding backward per step (beta 0)")
-        E.embed_bwd(ids, dh, f.g("wte"), f.g("wpe"), self.cfg.dropout, self.seed, step, row0, beta, keys=keys, sq=sq,
+        E.embed_bwd(ids, dh, f.g("wte"), f.g("wpe") if f.has("wpe") else None, self.cfg.dropout, self.seed, step, row0, beta, keys=keys, sq=sq,
                     prev_keys=prev, prev_valid=self._emb_prev_valid)
         if prev is not None:
             self._emb_prev_valid = True  # from the next call on only the rows written here are zeroed
@@ -409,6 +423,7 @@ class GPTStage:
         if y1q is None:
             y1q = MX.quant_mxfp8(y1)
         qkv = MX.linear_mxfp8(y1q, f.wmx(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=act)
+        self._rope(qkv, batch)
         o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
         o = o.view(batch * T, -1)
         oq = MX.quant_mxfp8(o)
@@ -451,6 +466,7 @@ class GPTStage:
             qkv = F8.linear_fp8(F8.quant_e4m3(y1), f.w8(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=self.act_dtype)
         else:
             qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
+        self._rope(qkv, batch)
         o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
         o = o.view(batch * T, -1)
         oq = F8.quant_e4m3(o) if fp8 else None
@@ -556,6 +572,7 @@ class GPTStage:
                                    out_dtype=self.act_dtype, pair=False)
         dqkv = A.attn_bwd(qkv.view(batch, T, -1), o.view(batch, T, -1), lse, do.view(batch, T, -1),
                           self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local).view(batch * T, -1)
+        self._rope(dqkv, batch, inverse=True)
         wtq = f.wt(p + "qkv.w")
         if self._fuse_bwd and wtq is not None:
             bg = self._prev_fc2b(l)
@@ -599,6 +616,7 @@ class GPTStage:
         y1l, mu1, rs1 = LN.layernorm_fwd(x, f.p(p + "ln1.g"), f.p(p + "ln1.b"), self.eps, self.act_dtype)
         y1 = tp.all_gather_rows(y1l)
         qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
+        self._rope(qkv, batch)
         o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
         o = o.view(rows, -1)
         x2 = self._row_parallel_sp(o, p + "out.w", resid=x, bias=f.p(p + "out.b"))
@@ -648,6 +666,7 @@ class GPTStage:
                                    out_dtype=self.act_dtype, pair=False)
         dqkv = A.attn_bwd(qkv.view(batch, T, -1), o.view(batch, T, -1), lse, do.view(batch, T, -1),
                           self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local).view(rows, -1)
+        self._rope(dqkv, batch, inverse=True)
         dy1 = self._tp_rs(self._dgrad_wgrad(dqkv, p + "qkv", y1, beta, red, pair=True))
         out = self._ln_bwd(dy1, x, p + "ln1", mu1, rs1, dx2, beta, bias_grad=self._prev_fc2b(l))
         if dx_hook is not None:

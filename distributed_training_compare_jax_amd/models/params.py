@@ -97,10 +97,10 @@ def head_param_specs(cfg: ModelConfig, part: int = 0, parts: int = 1) -> List[Pa
 
 def embed_param_specs(cfg: ModelConfig) -> List[ParamSpec]:
     D = cfg.d_model
-    return [
-        ParamSpec("wpe", (cfg.max_seq_len, D), "embed", D, "rep", -1, False),
-        ParamSpec("wte", (cfg.vocab_size, D), "embed", D, "rep", -1, False),
-    ]
+    wte = ParamSpec("wte", (cfg.vocab_size, D), "embed", D, "rep", -1, False)
+    if cfg.pos_emb == "rope":  # rotary embeddings: no position table
+        return [wte]
+    return [ParamSpec("wpe", (cfg.max_seq_len, D), "embed", D, "rep", -1, False), wte]
 
 
 def all_param_specs(cfg: ModelConfig) -> List[ParamSpec]:

@@ -89,7 +89,19 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
     D, H = cfg.d_model, cfg.n_heads
     hd = D // H
     eps = cfg.layernorm_eps
-    h = params["wte"][ids.long()] + params["wpe"][:T][None]
+    rope = cfg.pos_emb == "rope"  # rotary embeddings on q and k in place of the position table (ops/rope.py)
+    h = params["wte"][ids.long()]
+    if rope:
+        from ..ops.rope import rope_table
+
+        tab = rope_table(T, hd, cfg.rope_theta).to(device=h.device, dtype=h.dtype)
+        cos, sin = tab[None, :, None, :, 0], tab[None, :, None, :, 1]  # [1, T, 1, hd/2]
+
+        def rot(t):  # [B, T, heads, hd]: rotate-half pairing, element i with i + hd/2
+            lo, hi = t[..., :hd // 2], t[..., hd // 2:]
+            return torch.cat([lo * cos - hi * sin, hi * cos + lo * sin], -1)
+    else:
+        h = h + params["wpe"][:T][None]
     if cfg.dropout > 0:
         keep = dropout_keep_mask(B * T, D, row0 * T, cfg.dropout, seed, step).view(B, T, D).to(h.device)
         h = torch.where(keep, h / (1 - cfg.dropout), torch.zeros_like(h))
@@ -110,8 +122,10 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
         # grouped-query attention (cfg.n_kv_heads): rows [H | Hkv | Hkv] x hd, every K/V head repeated for its group
         Hkv = cfg.kv_heads
         q, k, v = qkv.split([H * hd, Hkv * hd, Hkv * hd], -1)
-        q = q.view(B, T, H, hd)
-        k, v = (t.view(B, T, Hkv, hd).repeat_interleave(H // Hkv, 2) for t in (k, v))
+        q, k = q.view(B, T, H, hd), k.view(B, T, Hkv, hd)
+        if rope:
+            q, k = rot(q), rot(k)
+        k, v = (t.reshape(B, T, Hkv, hd).repeat_interleave(H // Hkv, 2) for t in (k, v))
         s = torch.einsum("bthd,bshd->bhts", q, k) * hd ** -0.5 + add_mask
         a = torch.softmax(s, -1)
         o = torch.einsum("bhts,bshd->bthd", a, v).reshape(B, T, D)

@@ -164,7 +164,9 @@ def _declare(lib):
         "dtc_embed_sort_bits": ([i], i),
         "dtc_embed_sort": ([vp, i, i, vp, vp], i),
         "dtc_embed_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, f, l, vp, l, i, vp, vp, i, vp], i),
-        "dtc_embed_sq_slots": ([i, i, i], l),
+        "dtc_embed_sq_slots": ([i, i, i, i], l),
+        # rotary position embeddings (csrc/rope.hip): x, tab, B, T, H, Hkv, head_dim, tab_rows, dtype, inverse, stream
+        "dtc_rope": ([vp, vp, i, i, i, i, i, i, i, i, vp], i),
         "dtc_attn_fwd": ([vp, vp, vp, i, i, i, i, i, f, vp], i),
         "dtc_attn_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, l, vp], i),
         "dtc_attn_bwd_workspace_bytes": ([i, i, i, i], l),

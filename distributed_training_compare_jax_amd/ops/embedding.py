@@ -16,6 +16,8 @@ double ``p``, 7 below the kernel's at p = 0.1, so about 1.6e-9 of the elements w
 
 from __future__ import annotations
 
+from typing import Optional
+
 import numpy as np
 import torch
 
@@ -62,13 +64,16 @@ def dropout_keep_mask(n_tokens: int, D: int, token0: int, p: float, seed: int, s
     return torch.from_numpy(keep.reshape(n_tokens, D))
 
 
-def embed_fwd(ids: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, p: float, seed: int,
+def embed_fwd(ids: torch.Tensor, wte: torch.Tensor, wpe: Optional[torch.Tensor], p: float, seed: int,
               step: torch.Tensor, row0: int) -> torch.Tensor:
-    """ids int32 [B,T] → h fp32 [B*T, D]."""
+    """ids int32 [B,T] → h fp32 [B*T, D].  ``wpe=None``: no position table (``pos_emb: rope``), ``h =
+    dropout(wte[ids])``."""
     B, T = ids.shape
     D = wte.shape[1]
     if not ids.is_cuda:
-        h = wte[ids.long()].float() + wpe[:T].float()[None]
+        h = wte[ids.long()].float()
+        if wpe is not None:
+            h = h + wpe[:T].float()[None]
         h = h.reshape(B * T, D)
         if p > 0.0:
             keep = dropout_keep_mask(B * T, D, row0 * T, p, seed, int(step.item()))
@@ -76,19 +81,20 @@ def embed_fwd(ids: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, p: float,
         return h
     assert ids.dtype == torch.int32 and ids.is_contiguous() and wte.dtype == torch.float32
     h = torch.empty(B * T, D, dtype=torch.float32, device=ids.device)
-    N.check(N.lib().dtc_embed_fwd(ids.data_ptr(), wte.data_ptr(), wpe.data_ptr(), h.data_ptr(), B, T, D,
+    N.check(N.lib().dtc_embed_fwd(ids.data_ptr(), wte.data_ptr(), N.ptr(wpe), h.data_ptr(), B, T, D,
                                   wte.shape[0], p, seed, step.data_ptr(), row0, N.stream_ptr(ids.device)),
             "dtc_embed_fwd")
     return h
 
 
-def embed_sq_slots(B: int, T: int, D: int) -> int:
-    """Partial slots :func:`embed_bwd` writes into ``sq`` (``dtc_embed_sq_slots``)."""
-    return int(N.lib().dtc_embed_sq_slots(B, T, D))
+def embed_sq_slots(B: int, T: int, D: int, wpe: bool = True) -> int:
+    """Partial slots :func:`embed_bwd` writes into ``sq`` (``dtc_embed_sq_slots``); ``wpe=False``: of a call without
+    a position table (``dwpe=None``), which has no dwpe slots."""
+    return int(N.lib().dtc_embed_sq_slots(B, T, D, 1 if wpe else 0))
 
 
-def embed_bwd(ids: torch.Tensor, dh: torch.Tensor, dwte: torch.Tensor, dwpe: torch.Tensor, p: float, seed: int,
-              step: torch.Tensor, row0: int, beta: float = 0.0, keys: torch.Tensor = None, sq: torch.Tensor = None,
+def embed_bwd(ids: torch.Tensor, dh: torch.Tensor, dwte: torch.Tensor, dwpe: Optional[torch.Tensor], p: float,
+              seed: int, step: torch.Tensor, row0: int, beta: float = 0.0, keys: torch.Tensor = None, sq: torch.Tensor = None,
               prev_keys: torch.Tensor = None, prev_valid: bool = False):
     """dwte (β·)+= scatter_add(ids, dropout'(dh)); dwpe (β·)+= Σ_b dropout'(dh).
 
@@ -98,7 +104,7 @@ def embed_bwd(ids: torch.Tensor, dh: torch.Tensor, dwte: torch.Tensor, dwpe: tor
     of the new grads (the gradient norm's share of both tables without reading them again).
     ``prev_keys`` (GPU, beta = 0, one sort window): int32 [B*T] that holds the previous call's sort keys for this
     same ``dwte`` (``prev_valid``) -- only their rows are zeroed instead of the whole table -- and receives this
-    call's keys."""
+    call's keys.  ``dwpe=None``: no position table (``pos_emb: rope``): nothing is launched or summed for it."""
     B, T = ids.shape
     D = dh.shape[1]
     if not ids.is_cuda:
@@ -108,13 +114,15 @@ def embed_bwd(ids: torch.Tensor, dh: torch.Tensor, dwte: torch.Tensor, dwpe: tor
             g = torch.where(keep, g / (1.0 - p), torch.zeros_like(g))
         if beta == 0.0:
             dwte.zero_()
-            dwpe.zero_()
+            if dwpe is not None:
+                dwpe.zero_()
         dwte.index_add_(0, ids.reshape(-1).long(), g)
-        dwpe[:T].add_(g.view(B, T, D).sum(0))
+        if dwpe is not None:
+            dwpe[:T].add_(g.view(B, T, D).sum(0))
         return
     if sq is not None:
         assert beta == 0.0 and B * T <= SORT_MAX and sq.dtype == torch.float32 and sq.is_contiguous()
-        assert sq.numel() == embed_sq_slots(B, T, dh.shape[1]), (sq.numel(), B, T)
+        assert sq.numel() == embed_sq_slots(B, T, dh.shape[1], dwpe is not None), (sq.numel(), B, T)
     if prev_keys is not None:
         assert beta == 0.0 and B * T <= SORT_MAX and prev_keys.numel() == B * T and prev_keys.dtype == torch.int32
     if B * T > SORT_MAX:  # sort capacity of one workgroup: accumulate row chunks in order
@@ -128,7 +136,7 @@ def embed_bwd(ids: torch.Tensor, dh: torch.Tensor, dwte: torch.Tensor, dwpe: tor
         keys = embed_sort_keys(ids, dwte.shape[0])
     assert keys.numel() == B * T and dh.shape[0] == B * T and dh.is_contiguous()
     P = torch.empty(B * T, D, dtype=torch.float32, device=dh.device)
-    N.check(N.lib().dtc_embed_bwd(keys.data_ptr(), dh.data_ptr(), dwte.data_ptr(), dwpe.data_ptr(), P.data_ptr(), B,
+    N.check(N.lib().dtc_embed_bwd(keys.data_ptr(), dh.data_ptr(), dwte.data_ptr(), N.ptr(dwpe), P.data_ptr(), B,
                                   T, D, dwte.shape[0], p, seed, step.data_ptr(), row0, 1 if beta != 0.0 else 0,
                                   N.ptr(sq), N.ptr(prev_keys), 1 if prev_valid else 0, N.stream_ptr(ids.device)),
             "dtc_embed_bwd")

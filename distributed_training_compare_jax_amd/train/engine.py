@@ -371,9 +371,10 @@ class Engine:
             ends = [self.flat.range_of([n for n in names if n.startswith(f"h.{l}.")])[1] for l in self.layout.layers]
             head = [n for n in names if n.startswith("lm_head") or n.startswith("lnf")]
             bnd = ends + ([self.flat.range_of(head)[1]] if head else [])
+        emb_names = tuple(n for n in ("wte", "wpe") if n in self.flat.slots)  # pos_emb: rope has no wpe
         self.buckets = GradBuckets(self.flat, m.dp_group, dp, self.program, train_cfg.dp_bucket_mb,
                                    tail_mb=train_cfg.dp_tail_mb,
-                                   local_names=("wte", "wpe") if self.embed_gather else (), boundaries=bnd,
+                                   local_names=emb_names if self.embed_gather else (), boundaries=bnd,
                                    payload=train_cfg.dp_grad_dtype, active=self.dp_comm,
                                    transport="p2p" if self.zero_p2p else train_cfg.dp_comm)
         if self.zero_p2p:
@@ -1086,10 +1087,10 @@ class Engine:
         # rows): no 154 MB norm pass over a table whose untouched rows are zero (GPT-2 small: -25 us/step)
         emb = 0
         if self._emb_fused_norm():
-            for name in ("wte", "wpe"):
+            for name in (n for n in ("wte", "wpe") if n in self.flat.slots):  # pos_emb: rope has no wpe
                 g = self.flat.g(name)
                 ranges.append(((g.data_ptr() - base) // 4, g.numel()))
-            emb = E.embed_sq_slots(self.b_local, self.T, self._D)
+            emb = E.embed_sq_slots(self.b_local, self.T, self._D, wpe="wpe" in self.flat.slots)
         part = self.opt.set_fused_sumsq(ranges, nwg + emb)
         st.use_wgrad_sumsq(part[:nwg], problems)
         if emb:

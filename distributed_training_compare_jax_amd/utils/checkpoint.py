@@ -51,7 +51,7 @@ def save(eng, output_dir: str, step: int):
                 lr_schedule=eng.ocfg.schedule_key(), param_groups=eng.ocfg.groups_key(),
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
                 vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab),
-                n_kv_heads=int(eng.mcfg.kv_heads))
+                n_kv_heads=int(eng.mcfg.kv_heads), pos_emb=eng.mcfg.pos_emb, rope_theta=float(eng.mcfg.rope_theta))
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
         json.dump(meta, fh)
 
@@ -136,6 +136,12 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
     if kv_ck != kv_now:
         raise ValueError(f"checkpoint was written with n_kv_heads={kv_ck}, this run has n_kv_heads={kv_now}: the fused "
                          "qkv projection has other rows")
+    # the position scheme decides whether wpe exists and what the qkv weights mean (before the field: learned)
+    pos_ck, pos_now = m0.get("pos_emb", "learned"), eng.mcfg.pos_emb
+    th_ck, th_now = float(m0.get("rope_theta", eng.mcfg.rope_theta)), float(eng.mcfg.rope_theta)
+    if pos_ck != pos_now or (pos_now == "rope" and th_ck != th_now):
+        raise ValueError(f"checkpoint was written with pos_emb={pos_ck!r} (rope_theta={th_ck!r}), this run has "
+                         f"pos_emb={pos_now!r} (rope_theta={th_now!r}): resume with the values that wrote it")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
     for r, m in metas.items():
