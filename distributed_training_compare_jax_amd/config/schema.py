@@ -93,6 +93,12 @@ are optional and default to the reference behaviour:
   ``csrc/rope.hip``: one in-place pass over ``qkv`` after its GEMM, the transposed one over ``dqkv`` after the attention
   backward).  Only position differences reach the scores, so ``doc_mask_token`` needs no per-document reset.  ``head_dim``
   must be even (GPU: 32, 64 or 128); every dtype, layout and forward GEMM mode.  A checkpoint records both values.
+* ``ModelConfig.norm`` (``layernorm`` | ``rmsnorm``, default ``layernorm``): ``rmsnorm`` normalises every block's two
+  norms and the final one by the root mean square alone, ``y = x * rsqrt(mean(x^2) + layernorm_eps) * g`` (``ops/rmsnorm.py``,
+  ``csrc/rmsnorm.hip``), with no mean and no bias: the parameters ``h.*.ln1.b``, ``h.*.ln2.b`` and ``lnf.b`` do not exist
+  (:meth:`ModelConfig.num_params` follows; the Dense biases stay).  ``d_model % 4 == 0`` and ``<= 8192``; every dtype and
+  layout with ``fwd_gemm_dtype: bf16`` (the FP8 / MXFP8 forwards are refused); the GEMM-fused LayerNorm (``DTC_LN_FUSE``)
+  is off under it.  A checkpoint records the value.
 """
 
 from __future__ import annotations
@@ -124,12 +130,15 @@ class ModelConfig:
     n_kv_heads: Optional[int] = None  # grouped-query attention: K/V heads, a divisor of n_heads (None: n_heads)
     pos_emb: str = "learned"  # learned (the wpe table) | rope (rotary embeddings on Q and K, no wpe: ops/rope.py)
     rope_theta: float = 10000.0  # rope: the angles are t * rope_theta**(-2i/head_dim)
+    norm: str = "layernorm"  # layernorm (scale and bias) | rmsnorm (scale only, no mean: ops/rmsnorm.py)
 
     def __post_init__(self):
         import math
 
         if self.pos_emb not in ("learned", "rope"):
             raise ValueError(f"pos_emb={self.pos_emb!r}: expected 'learned' or 'rope'")
+        if self.norm not in ("layernorm", "rmsnorm"):
+            raise ValueError(f"norm={self.norm!r}: expected 'layernorm' or 'rmsnorm'")
         th = self.rope_theta
         if isinstance(th, bool) or not isinstance(th, (int, float)) or not math.isfinite(th) or th <= 0:
             raise ValueError(f"rope_theta={th!r}: expected a finite number > 0")
@@ -165,7 +174,8 @@ class ModelConfig:
         Q = self.qkv_rows  # 3 D when multi-head
         per_layer = (Q + D) * D + (Q + D) + D * F + F + F * D + D + 4 * D
         pos = T * D if self.pos_emb == "learned" else 0  # rope has no position table
-        return V * D + pos + L * per_layer + 2 * D + D * V + V
+        nb = (2 * L + 1) * D if self.norm == "rmsnorm" else 0  # rmsnorm has no norm biases
+        return V * D + pos + L * per_layer + 2 * D + D * V + V - nb
 
     def flops_per_token(self, causal: bool = True) -> float:
         """Matmul FLOPs per token, fwd+bwd: 6 * N_matmul + attention.  ``causal`` (default): the useful

@@ -31,6 +31,7 @@ from ..ops import attention as A
 from ..ops import embedding as E
 from ..ops import gemm as G
 from ..ops import layernorm as LN
+from ..ops import rmsnorm as RN
 from ..ops import fp8 as F8
 from ..ops import mxfp8 as MX
 from ..ops import ln_fused as LF
@@ -158,6 +159,7 @@ class GPTStage:
         self.v_start = part * (cfg.padded_vocab // parts) + self.tp.rank * self.v_local
         self.v_valid = max(0, min(self.v_local, cfg.vocab_size - self.v_start))
         self.eps = cfg.layernorm_eps
+        self.rms = cfg.norm == "rmsnorm"  # every norm site goes through _norm / _add_norm / _ln_bwd
         # Deferred weight gradients (set_wgrad_group): the dgrad chain runs alone and every (dY, X, dW, db)
         # of wgrad_group consecutive layers (0 = the whole stage, + the lm_head) goes out as ONE grouped
         # launch of whole 256^2 tiles (ops/gemm.py wgrad_group)
@@ -273,6 +275,8 @@ class GPTStage:
         D, L = self.cfg.d_model, len(self.layout.layers)
         if self.tp.size != 1 or not L or not LF.supported(tokens, D, 64) or not (fwd or bwd):
             return False
+        if self.rms:  # the GEMM epilogues (EPI_RESID_LN / EPI_LN_BWD) are LayerNorm arithmetic
+            return False
         self.ln_sync = LF.LnSync(self.flat.device, tokens, D, nsites=4 * L, step=step)
         self._fuse_fwd, self._fuse_bwd = bool(fwd), bool(bwd)
         return True
@@ -301,6 +305,8 @@ class GPTStage:
         out = {l: [f"h.{l}.{n}" for n in ("ln1.g", "ln1.b", "ln2.g", "ln2.b", "out.b", "fc2.b")]
                for l in self.layout.layers}
         out["head"] = ["lnf.g", "lnf.b"]
+        if self.rms:  # no norm biases
+            out = {k: [n for n in v if not n.endswith(("ln1.b", "ln2.b", "lnf.b"))] for k, v in out.items()}
         return out
 
     def _sp_index(self, names, dev) -> torch.Tensor:
@@ -324,6 +330,23 @@ class GPTStage:
         buf = g.index_select(0, idx)
         self.tp.all_reduce_(buf)
         g.index_copy_(0, idx, buf)
+
+    def _norm(self, x: torch.Tensor, ln: str):
+        """Norm ``ln`` (``h.<l>.ln1`` / ``h.<l>.ln2`` / ``lnf``) of the fp32 rows ``x`` by ``cfg.norm`` -> ``(y, mean,
+        rstd)``, what the backward gets back; ``mean`` is None under ``rmsnorm`` (it has none)."""
+        f = self.flat
+        if self.rms:
+            y, rs = RN.rmsnorm_fwd(x, f.p(ln + ".g"), self.eps, self.act_dtype)
+            return y, None, rs
+        return LN.layernorm_fwd(x, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
+
+    def _add_norm(self, d: torch.Tensor, resid: torch.Tensor, ln: str):
+        """``x = d + resid`` and :meth:`_norm` of it in one pass -> ``(x, (y, mean, rstd))``."""
+        f = self.flat
+        if self.rms:
+            x, (y, rs) = RN.add_rmsnorm_fwd(d, resid, f.p(ln + ".g"), self.eps, self.act_dtype)
+            return x, (y, None, rs)
+        return LN.add_layernorm_fwd(d, resid, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
 
     def _ln_site(self, l: int, k: int, backward: bool) -> int:
         """Execution-order index of a fused LayerNorm call: forward k = 0 (out_proj → ln2) / 1 (fc2 →
@@ -438,7 +461,7 @@ class GPTStage:
         if _ADD_LN and nxt is not None:
             br = MX.linear_mxfp8(gq, f.wmx(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype)
             if nxt == "lnf":
-                x3, ctx["lnf_pre"] = LN.add_layernorm_fwd(br, x2, f.p("lnf.g"), f.p("lnf.b"), self.eps, act)
+                x3, ctx["lnf_pre"] = self._add_norm(br, x2, "lnf")
             else:
                 x3, ctx[("ln1", l + 1)], ctx[("ln1_mx", l + 1)] = MX.add_layernorm_fwd_mx(
                     br, x2, f.p(nxt + ".g"), f.p(nxt + ".b"), self.eps, act)
@@ -459,7 +482,7 @@ class GPTStage:
         T = x.shape[0] // batch
         pre = ctx.pop(("ln1", l), None)  # LN1 already produced by the previous layer's fc2 GEMM
         if pre is None:
-            pre = LN.layernorm_fwd(x, f.p(p + "ln1.g"), f.p(p + "ln1.b"), self.eps, self.act_dtype)
+            pre = self._norm(x, p + "ln1")
         y1, mu1, rs1 = pre
         fp8 = self.fp8  # the four layer GEMMs on e4m3 operands (enable_fp8_forward); ctx keeps the same tensors
         if fp8:
@@ -475,21 +498,20 @@ class GPTStage:
                                                     f.p(p + "ln2.b"), self.eps, self.ln_sync, self._ln_site(l, 0, False))
         elif self.tp_bf16:
             x2 = self._row_parallel(o, p + "out.w", resid=x, bias=f.p(p + "out.b"))
-            y2, mu2, rs2 = LN.layernorm_fwd(x2, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, self.act_dtype)
+            y2, mu2, rs2 = self._norm(x2, p + "ln2")
         elif tp.size == 1 and _ADD_LN:
             # residual add in the LayerNorm pass (the GEMM stores o·Wᵀ + b; its epilogue skips the fp32
             # residual read) -- same fp32 arithmetic, (acc + b) + x
             br = (F8.linear_fp8(oq, f.w8(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype) if fp8 else
                   G.linear(o, f.w(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype))
-            x2, (y2, mu2, rs2) = LN.add_layernorm_fwd(br, x, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps,
-                                                      self.act_dtype)
+            x2, (y2, mu2, rs2) = self._add_norm(br, x, p + "ln2")
         else:
             if fp8:
                 x2 = F8.linear_resid_fp8(oq, f.w8(p + "out.w"), f.p(p + "out.b"), x)
             else:
                 x2 = G.linear_resid(o, f.w(p + "out.w"), f.p(p + "out.b") if lead else None, x if lead else None)
             tp.all_reduce_(x2)
-            y2, mu2, rs2 = LN.layernorm_fwd(x2, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, self.act_dtype)
+            y2, mu2, rs2 = self._norm(x2, p + "ln2")
         if fp8:
             u, gact = F8.linear_gelu_fp8(F8.quant_e4m3(y2), f.w8(p + "fc1.w"), f.p(p + "fc1.b"), out_dtype=self.act_dtype)
             gq = F8.quant_e4m3(gact)
@@ -504,7 +526,7 @@ class GPTStage:
         elif tp.size == 1 and _ADD_LN and nxt is not None and not self.tp_bf16:
             br = (F8.linear_fp8(gq, f.w8(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype) if fp8 else
                   G.linear(gact, f.w(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype))
-            x3, pre_next = LN.add_layernorm_fwd(br, x2, f.p(nxt + ".g"), f.p(nxt + ".b"), self.eps, self.act_dtype)
+            x3, pre_next = self._add_norm(br, x2, nxt)
             ctx[("ln1", l + 1) if nxt != "lnf" else "lnf_pre"] = pre_next
         elif self.tp_bf16:
             x3 = self._row_parallel(gact, p + "fc2.w", resid=x2, bias=f.p(p + "fc2.b"))
@@ -613,14 +635,14 @@ class GPTStage:
         f, p, tp = self.flat, f"h.{l}.", self.tp
         rows = x.shape[0] * tp.size
         T = rows // batch
-        y1l, mu1, rs1 = LN.layernorm_fwd(x, f.p(p + "ln1.g"), f.p(p + "ln1.b"), self.eps, self.act_dtype)
+        y1l, mu1, rs1 = self._norm(x, p + "ln1")
         y1 = tp.all_gather_rows(y1l)
         qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
         self._rope(qkv, batch)
         o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
         o = o.view(rows, -1)
         x2 = self._row_parallel_sp(o, p + "out.w", resid=x, bias=f.p(p + "out.b"))
-        y2l, mu2, rs2 = LN.layernorm_fwd(x2, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, self.act_dtype)
+        y2l, mu2, rs2 = self._norm(x2, p + "ln2")
         y2 = tp.all_gather_rows(y2l)
         u, gact = G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))
         x3 = self._row_parallel_sp(gact, p + "fc2.w", resid=x2, bias=f.p(p + "fc2.b"))
@@ -736,8 +758,13 @@ class GPTStage:
         f = self.flat
         dx_c = None if self.act_dtype == torch.float32 else torch.empty(dy.shape, dtype=self.act_dtype,
                                                                         device=dy.device)
-        dx = LN.layernorm_bwd(dy, x, f.p(ln + ".g"), mu, rs, dres, f.g(ln + ".g"), f.g(ln + ".b"), beta,
-                              out_c=dx_c, dbias=None if bias_grad is None else f.g(bias_grad), red=self.red)
+        dbias = None if bias_grad is None else f.g(bias_grad)
+        if self.rms:
+            dx = RN.rmsnorm_bwd(dy, x, f.p(ln + ".g"), rs, dres, f.g(ln + ".g"), beta, out_c=dx_c, dbias=dbias,
+                                red=self.red)
+        else:
+            dx = LN.layernorm_bwd(dy, x, f.p(ln + ".g"), mu, rs, dres, f.g(ln + ".g"), f.g(ln + ".b"), beta,
+                                  out_c=dx_c, dbias=dbias, red=self.red)
         return dx, (dx if dx_c is None else dx_c)
 
     def stage_forward(self, x: torch.Tensor, batch: int, ctx: Dict, keep: bool = True) -> torch.Tensor:
@@ -770,8 +797,7 @@ class GPTStage:
         self._await_params("head")
         f = self.flat
         pre = ctx.pop("lnf_pre", None)  # produced by the last layer's fc2 GEMM (fused LayerNorm)
-        yf, muf, rsf = pre if pre is not None else LN.layernorm_fwd(x, f.p("lnf.g"), f.p("lnf.b"), self.eps,
-                                                                     self.act_dtype)
+        yf, muf, rsf = pre if pre is not None else self._norm(x, "lnf")
         if self.sp:
             yf = self.tp.all_gather_rows(yf)  # the vocab-parallel lm_head reads every row
         lab = labels.reshape(-1)
@@ -805,7 +831,7 @@ class GPTStage:
         f = self.flat
         pre = ctx.pop("lnf_pre", None) if ctx is not None else None
         if pre is None:
-            pre = LN.layernorm_fwd(x, f.p("lnf.g"), f.p("lnf.b"), self.eps, self.act_dtype)
+            pre = self._norm(x, "lnf")
         yf = pre[0]
         if self.sp:
             yf = self.tp.all_gather_rows(yf)
@@ -851,7 +877,7 @@ class GPTStage:
         """Part 0: the final LayerNorm of the stage output -- the message to part 1 (compute dtype)."""
         f = self.flat
         self._await_params("head")
-        yf, muf, rsf = LN.layernorm_fwd(x, f.p("lnf.g"), f.p("lnf.b"), self.eps, self.act_dtype)
+        yf, muf, rsf = self._norm(x, "lnf")
         ctx["head_yf"] = (x, yf, muf, rsf)
         return yf
 

@@ -64,7 +64,7 @@ def layer_param_specs(cfg: ModelConfig, l: int) -> List[ParamSpec]:
     Q, kv = cfg.qkv_rows, (0 if cfg.kv_heads == H else cfg.kv_heads)
     p = f"h.{l}."
     # backward production order inside a block
-    return [
+    specs = [
         ParamSpec(p + "fc2.w", (D, F), "dense", F, "cols", l, True),
         ParamSpec(p + "fc2.b", (D,), "zeros", F, "rep", l, True),
         ParamSpec(p + "fc1.w", (F, D), "dense", D, "rows", l, True),
@@ -78,6 +78,9 @@ def layer_param_specs(cfg: ModelConfig, l: int) -> List[ParamSpec]:
         ParamSpec(p + "ln1.g", (D,), "ones", D, "rep", l, True),
         ParamSpec(p + "ln1.b", (D,), "zeros", D, "rep", l, True),
     ]
+    if cfg.norm == "rmsnorm":  # a scale only: no norm biases
+        specs = [s for s in specs if not s.name.endswith((".ln1.b", ".ln2.b"))]
+    return specs
 
 
 def head_param_specs(cfg: ModelConfig, part: int = 0, parts: int = 1) -> List[ParamSpec]:
@@ -90,8 +93,9 @@ def head_param_specs(cfg: ModelConfig, part: int = 0, parts: int = 1) -> List[Pa
         ParamSpec("lm_head.b", (Vp,), "zeros", D, "rows", -2, True, valid_rows=cfg.vocab_size, vpart=vp),
     ]
     if part == 0:
-        out += [ParamSpec("lnf.g", (D,), "ones", D, "rep", -2, True),
-                ParamSpec("lnf.b", (D,), "zeros", D, "rep", -2, True)]
+        out += [ParamSpec("lnf.g", (D,), "ones", D, "rep", -2, True)]
+        if cfg.norm != "rmsnorm":
+            out += [ParamSpec("lnf.b", (D,), "zeros", D, "rep", -2, True)]
     return out
 
 

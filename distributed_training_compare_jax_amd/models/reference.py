@@ -89,6 +89,10 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
     D, H = cfg.d_model, cfg.n_heads
     hd = D // H
     eps = cfg.layernorm_eps
+    if cfg.norm == "rmsnorm":  # x * rsqrt(mean(x^2) + eps) * g, no bias (ops/rmsnorm.py)
+        norm = lambda t, g, b: t * torch.rsqrt(t.pow(2).mean(-1, keepdim=True) + eps) * params[g]  # noqa: E731
+    else:
+        norm = lambda t, g, b: F.layer_norm(t, (D,), params[g], params[b], eps)  # noqa: E731
     rope = cfg.pos_emb == "rope"  # rotary embeddings on q and k in place of the position table (ops/rope.py)
     h = params["wte"][ids.long()]
     if rope:
@@ -117,7 +121,7 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
     for l in range(cfg.n_layers):
         p = lambda n: params[f"h.{l}.{n}"]  # noqa: E731
         r = h
-        x = F.layer_norm(h, (D,), p("ln1.g"), p("ln1.b"), eps)
+        x = norm(h, f"h.{l}.ln1.g", f"h.{l}.ln1.b")
         qkv = mm(x, p("qkv.w")) + p("qkv.b")
         # grouped-query attention (cfg.n_kv_heads): rows [H | Hkv | Hkv] x hd, every K/V head repeated for its group
         Hkv = cfg.kv_heads
@@ -131,9 +135,9 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
         o = torch.einsum("bhts,bshd->bthd", a, v).reshape(B, T, D)
         h = mm(o, p("out.w")) + p("out.b") + r
         r = h
-        x = F.layer_norm(h, (D,), p("ln2.g"), p("ln2.b"), eps)
+        x = norm(h, f"h.{l}.ln2.g", f"h.{l}.ln2.b")
         x = _gelu_tanh(mm(x, p("fc1.w")) + p("fc1.b"))
         h = mm(x, p("fc2.w")) + p("fc2.b") + r
-    x = F.layer_norm(h, (D,), params["lnf.g"], params["lnf.b"], eps)
+    x = norm(h, "lnf.g", "lnf.b")
     V = cfg.vocab_size
     return x @ params["lm_head.w"][:V].t() + params["lm_head.b"][:V]

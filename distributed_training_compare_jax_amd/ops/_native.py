@@ -114,6 +114,13 @@ def _declare(lib):
         "dtc_add_layernorm_fwd_bf16": ([vp, vp, vp, vp, vp, vp, vp, vp, i, i, f, i, vp], i),
         "dtc_layernorm_bwd": ([vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, l, i, vp], i),
         "dtc_layernorm_bwd_workspace_bytes": ([i, i], l),
+        # RMSNorm (csrc/rmsnorm.hip): fwd x, g, y, rstd, M, D, eps, out_f32, stream; the add forms take (d, resid, x_out)
+        # first; bwd dy, dy_f32, x, g, rstd, dres, dx, dx_c, dg, dbias, M, D, accumulate, ws, ws_bytes, defer, stream
+        "dtc_rmsnorm_fwd": ([vp, vp, vp, vp, i, i, f, i, vp], i),
+        "dtc_add_rmsnorm_fwd": ([vp, vp, vp, vp, vp, vp, i, i, f, i, vp], i),
+        "dtc_add_rmsnorm_fwd_bf16": ([vp, vp, vp, vp, vp, vp, i, i, f, i, vp], i),
+        "dtc_rmsnorm_bwd": ([vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, l, i, vp], i),
+        "dtc_rmsnorm_bwd_workspace_bytes": ([i, i], l),
         "dtc_colsum": ([vp, i, i, i, l, vp, f, vp, l, i, vp], i),
         "dtc_gemm_wgrad_split": ([i, i, i, i], i),
         "dtc_gemm_set_n8": ([i], i),

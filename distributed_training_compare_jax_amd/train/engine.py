@@ -172,6 +172,11 @@ class Engine:
                        "kernels are the 32-row family, head_dim 64 or 128")
             if why:
                 raise ValueError(f"n_kv_heads={model_cfg.kv_heads} cannot be combined with {why}")
+        # norm: rmsnorm (ops/rmsnorm.py) runs under every layout, dtype and schedule; what it does not cover is refused
+        # here, by name
+        if model_cfg.norm == "rmsnorm" and train_cfg.fwd_gemm_dtype != "bf16":
+            raise ValueError(f"norm=rmsnorm cannot be combined with fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the MXFP8 "
+                             "quantiser is fused into the LayerNorm kernel, and the FP8 forwards have not been run with it)")
         # eval_every: the held-out evaluation (evaluate) -- what it does not cover is refused here, by name
         if train_cfg.eval_every > 0:
             if pp > 1:

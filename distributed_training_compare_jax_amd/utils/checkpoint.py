@@ -51,7 +51,8 @@ def save(eng, output_dir: str, step: int):
                 lr_schedule=eng.ocfg.schedule_key(), param_groups=eng.ocfg.groups_key(),
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
                 vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab),
-                n_kv_heads=int(eng.mcfg.kv_heads), pos_emb=eng.mcfg.pos_emb, rope_theta=float(eng.mcfg.rope_theta))
+                n_kv_heads=int(eng.mcfg.kv_heads), pos_emb=eng.mcfg.pos_emb, rope_theta=float(eng.mcfg.rope_theta),
+                norm=eng.mcfg.norm)
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
         json.dump(meta, fh)
 
@@ -142,6 +143,11 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
     if pos_ck != pos_now or (pos_now == "rope" and th_ck != th_now):
         raise ValueError(f"checkpoint was written with pos_emb={pos_ck!r} (rope_theta={th_ck!r}), this run has "
                          f"pos_emb={pos_now!r} (rope_theta={th_now!r}): resume with the values that wrote it")
+    # the norm decides whether the norm biases exist and what the scales mean (before the field: layernorm)
+    norm_ck, norm_now = m0.get("norm", "layernorm"), eng.mcfg.norm
+    if norm_ck != norm_now:
+        raise ValueError(f"checkpoint was written with norm={norm_ck!r}, this run has norm={norm_now!r}: resume with "
+                         "the value that wrote it")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
     for r, m in metas.items():
