@@ -99,6 +99,13 @@ are optional and default to the reference behaviour:
   (:meth:`ModelConfig.num_params` follows; the Dense biases stay).  ``d_model % 4 == 0`` and ``<= 8192``; every dtype and
   layout with ``fwd_gemm_dtype: bf16`` (the FP8 / MXFP8 forwards are refused); the GEMM-fused LayerNorm (``DTC_LN_FUSE``)
   is off under it.  A checkpoint records the value.
+* ``ModelConfig.mlp`` (``gelu`` | ``swiglu``, default ``gelu``): ``swiglu`` replaces ``fc2(gelu(fc1 x))`` by the gated MLP
+  ``fc2(silu(x·Wgᵀ + bg) * (x·Wuᵀ + bu))`` (``ops/swiglu.py``, ``csrc/swiglu.hip``).  ``d_ff`` stays the hidden width F;
+  ``h.*.fc1.w`` is ``[2F, D]`` (gate rows, then up rows, each its own lecun-normal kernel) and ``h.*.fc1.b`` ``[2F]``, ``fc2``
+  is unchanged; :meth:`ModelConfig.num_params` and :meth:`ModelConfig.flops_per_token` (three ``D·F`` matmuls a layer)
+  follow.  Tensor parallelism splits the gate and the up slab each evenly (``ParamSpec.tp: glu_rows``).  Every dtype and
+  layout with ``fwd_gemm_dtype: bf16`` (the FP8 / MXFP8 forwards are refused); the GEMM-fused LayerNorm (``DTC_LN_FUSE``)
+  is off under it.  A checkpoint records the value.
 """
 
 from __future__ import annotations
@@ -131,6 +138,7 @@ class ModelConfig:
     pos_emb: str = "learned"  # learned (the wpe table) | rope (rotary embeddings on Q and K, no wpe: ops/rope.py)
     rope_theta: float = 10000.0  # rope: the angles are t * rope_theta**(-2i/head_dim)
     norm: str = "layernorm"  # layernorm (scale and bias) | rmsnorm (scale only, no mean: ops/rmsnorm.py)
+    mlp: str = "gelu"  # gelu (fc2(gelu(fc1 x))) | swiglu (fc2(silu(gate x) * up x), fc1 = [gate; up]: ops/swiglu.py)
 
     def __post_init__(self):
         import math
@@ -139,6 +147,8 @@ class ModelConfig:
             raise ValueError(f"pos_emb={self.pos_emb!r}: expected 'learned' or 'rope'")
         if self.norm not in ("layernorm", "rmsnorm"):
             raise ValueError(f"norm={self.norm!r}: expected 'layernorm' or 'rmsnorm'")
+        if self.mlp not in ("gelu", "swiglu"):
+            raise ValueError(f"mlp={self.mlp!r}: expected 'gelu' or 'swiglu'")
         th = self.rope_theta
         if isinstance(th, bool) or not isinstance(th, (int, float)) or not math.isfinite(th) or th <= 0:
             raise ValueError(f"rope_theta={th!r}: expected a finite number > 0")
@@ -164,6 +174,11 @@ class ModelConfig:
         return (self.n_heads + 2 * self.kv_heads) * self.head_dim
 
     @property
+    def fc1_rows(self) -> int:
+        """Rows of ``fc1.w``: ``d_ff``, or ``2 d_ff`` (gate and up projection) under ``mlp: swiglu``."""
+        return 2 * self.d_ff if self.mlp == "swiglu" else self.d_ff
+
+    @property
     def padded_vocab(self) -> int:
         m = max(1, int(self.vocab_pad_multiple))
         return ((self.vocab_size + m - 1) // m) * m
@@ -172,7 +187,8 @@ class ModelConfig:
         """Parameter count of the reference architecture (unpadded vocab)."""
         D, F, V, T, L = self.d_model, self.d_ff, self.vocab_size, self.max_seq_len, self.n_layers
         Q = self.qkv_rows  # 3 D when multi-head
-        per_layer = (Q + D) * D + (Q + D) + D * F + F + F * D + D + 4 * D
+        F1 = self.fc1_rows  # 2 F under swiglu
+        per_layer = (Q + D) * D + (Q + D) + D * F1 + F1 + F * D + D + 4 * D
         pos = T * D if self.pos_emb == "learned" else 0  # rope has no position table
         nb = (2 * L + 1) * D if self.norm == "rmsnorm" else 0  # rmsnorm has no norm biases
         return V * D + pos + L * per_layer + 2 * D + D * V + V - nb
@@ -182,7 +198,7 @@ class ModelConfig:
         work of the causal attention, (T + 1) / 2 keys per query on average; ``causal=False``: the full
         T x T count SURVEY §2.4 / BASELINE.md's 1.715 TFLOP/step estimate use."""
         D, F, V, T, L = self.d_model, self.d_ff, self.vocab_size, self.max_seq_len, self.n_layers
-        mm = L * ((self.qkv_rows + D) * D + 2 * D * F) + D * V  # attention itself does not shrink with n_kv_heads
+        mm = L * ((self.qkv_rows + D) * D + D * (self.fc1_rows + F)) + D * V  # attention itself does not shrink with n_kv_heads
         keys = (T + 1) / 2.0 if causal else float(T)
         attn = L * 2 * keys * D  # QK^T + PV multiply-adds per token
         return 6.0 * mm + 3.0 * 2.0 * attn

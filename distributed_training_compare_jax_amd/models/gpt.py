@@ -32,6 +32,7 @@ from ..ops import embedding as E
 from ..ops import gemm as G
 from ..ops import layernorm as LN
 from ..ops import rmsnorm as RN
+from ..ops import swiglu as SW
 from ..ops import fp8 as F8
 from ..ops import mxfp8 as MX
 from ..ops import ln_fused as LF
@@ -128,7 +129,7 @@ class GPTStage:
         dev = torch.device(flat.device)
         # 512 MB window: a layer's split-K weight-gradient slabs (GPT-2 medium: 4 x ~67 MB) + LN partials;
         # past GPT-2 medium the window grows with a layer's fp32 weights (medium: 48 MB -> 512, gpt-1.3b: 192 MB -> 2048)
-        layer_bytes = 4 * (4 * cfg.d_model * cfg.d_model + 2 * cfg.d_model * cfg.d_ff)
+        layer_bytes = 4 * (4 * cfg.d_model * cfg.d_model + cfg.d_model * (cfg.fc1_rows + cfg.d_ff))
         self.red = GradReducer(dev, arena_mb=max(512, (32 * layer_bytes // 3) >> 20)) if dev.type == "cuda" else None
         self._bias_fused = set()  # layers whose fc2.b grad an upstream LN backward already produced
         # deferred optimizer (train/engine.py): params of layer l / "head" become valid when this
@@ -160,6 +161,7 @@ class GPTStage:
         self.v_valid = max(0, min(self.v_local, cfg.vocab_size - self.v_start))
         self.eps = cfg.layernorm_eps
         self.rms = cfg.norm == "rmsnorm"  # every norm site goes through _norm / _add_norm / _ln_bwd
+        self.glu = cfg.mlp == "swiglu"  # the bf16 MLP goes through _fc1 / _fc2_bwd
         # Deferred weight gradients (set_wgrad_group): the dgrad chain runs alone and every (dY, X, dW, db)
         # of wgrad_group consecutive layers (0 = the whole stage, + the lm_head) goes out as ONE grouped
         # launch of whole 256^2 tiles (ops/gemm.py wgrad_group)
@@ -277,6 +279,8 @@ class GPTStage:
             return False
         if self.rms:  # the GEMM epilogues (EPI_RESID_LN / EPI_LN_BWD) are LayerNorm arithmetic
             return False
+        if self.glu:  # the fused-LayerNorm fc1 dgrad was planned for K = F, not the gated fc1's 2F
+            return False
         self.ln_sync = LF.LnSync(self.flat.device, tokens, D, nsites=4 * L, step=step)
         self._fuse_fwd, self._fuse_bwd = bool(fwd), bool(bwd)
         return True
@@ -347,6 +351,33 @@ class GPTStage:
             x, (y, rs) = RN.add_rmsnorm_fwd(d, resid, f.p(ln + ".g"), self.eps, self.act_dtype)
             return x, (y, None, rs)
         return LN.add_layernorm_fwd(d, resid, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
+
+    def _fc1(self, y2: torch.Tensor, p: str):
+        """The first half of the MLP of block ``p`` by ``cfg.mlp`` -> ``(saved, act)``: the fc2 input ``act`` and what
+        :meth:`_fc2_bwd` gets back (``gelu'(u)``, or the gated pre-activations ``g | u`` under ``swiglu``)."""
+        f = self.flat
+        if self.glu:
+            return SW.swiglu_fc1(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))
+        return G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))  # u = gelu'(pre-activation)
+
+    def _fc2_bwd(self, dy: torch.Tensor, p: str, saved: torch.Tensor, act: torch.Tensor, beta: float):
+        """fc2's dgrad through the activation backward -> the gradient of the fc1 output, and fc2's weight gradient
+        (queued, or launched with the dgrad)."""
+        f, red = self.flat, self.red
+        wt2 = f.wt(p + "fc2.w")
+        if self.glu:
+            du = SW.swiglu_fc2_dgrad(dy, f.w(p + "fc2.w"), wt2, saved)
+            self._wg(dy, act, p + "fc2")
+        elif self._defer_wg:
+            # deferred weight gradients: the dgrad chain alone, (dY, X) pairs queued for the grouped launch
+            du = G.matmul_nt_dgelu(dy, wt2, saved) if wt2 is not None else G.matmul_nn_dgelu(dy, f.w(p + "fc2.w"), saved)
+            self._wg(dy, act, p + "fc2")
+        else:
+            # each Dense's dgrad and weight gradient share one launch (G.linear_backward), weight-gradient
+            # reductions go to the layer's batched launch; with a transposed fc2 weight the paired dgrad
+            # runs NT (+ GELU backward), both operands K-major
+            du = G.linear_backward(dy, f.w(p + "fc2.w"), act, f.g(p + "fc2.w"), beta, red=red, dgelu_u=saved, wt=wt2)
+        return du
 
     def _ln_site(self, l: int, k: int, backward: bool) -> int:
         """Execution-order index of a fused LayerNorm call: forward k = 0 (out_proj → ln2) / 1 (fc2 →
@@ -516,7 +547,7 @@ class GPTStage:
             u, gact = F8.linear_gelu_fp8(F8.quant_e4m3(y2), f.w8(p + "fc1.w"), f.p(p + "fc1.b"), out_dtype=self.act_dtype)
             gq = F8.quant_e4m3(gact)
         else:
-            u, gact = G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))  # u = gelu'(pre-activation)
+            u, gact = self._fc1(y2, p)
         # the LayerNorm that reads x3: the next layer's ln1, or the final one after the last layer
         nxt = f"h.{l + 1}.ln1" if (l + 1) in self.layout.layers else ("lnf" if self.layout.has_head else None)
         if self._fuse_fwd and nxt is not None:
@@ -553,22 +584,9 @@ class GPTStage:
         fc2b_fused = l in self._bias_fused
         self._bias_fused.discard(l)
         self._beta = beta
-        if self._defer_wg:
-            # deferred weight gradients: the dgrad chain alone, (dY, X) pairs queued for the grouped launch
-            wt2 = f.wt(p + "fc2.w")
-            du = (G.matmul_nt_dgelu(dx3_c, wt2, u) if wt2 is not None
-                  else G.matmul_nn_dgelu(dx3_c, f.w(p + "fc2.w"), u))
-            self._wg(dx3_c, gact, p + "fc2")
-            if not fc2b_fused:
-                G.colsum(dx3, f.g(p + "fc2.b"), beta, red=red)
-        else:
-            # each Dense's dgrad and weight gradient share one launch (G.linear_backward), weight-gradient
-            # reductions go to the layer's batched launch; with a transposed fc2 weight the paired dgrad
-            # runs NT (+ GELU backward), both operands K-major
-            du = G.linear_backward(dx3_c, f.w(p + "fc2.w"), gact, f.g(p + "fc2.w"), beta, red=red, dgelu_u=u,
-                                   wt=f.wt(p + "fc2.w"))
-            if not fc2b_fused:
-                G.colsum(dx3, f.g(p + "fc2.b"), beta, red=red)
+        du = self._fc2_bwd(dx3_c, p, u, gact, beta)
+        if not fc2b_fused:
+            G.colsum(dx3, f.g(p + "fc2.b"), beta, red=red)
         # paired launches measured per Dense (in-step, us): fc2 44.1 vs 46.8 and qkv 35.6 vs 38.1
         # separate; fc1 48.7 vs 48.1 and out_proj 22.4 vs 21.7 -> those two stay separate
         wt1 = f.wt(p + "fc1.w")
@@ -644,7 +662,7 @@ class GPTStage:
         x2 = self._row_parallel_sp(o, p + "out.w", resid=x, bias=f.p(p + "out.b"))
         y2l, mu2, rs2 = self._norm(x2, p + "ln2")
         y2 = tp.all_gather_rows(y2l)
-        u, gact = G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))
+        u, gact = self._fc1(y2, p)
         x3 = self._row_parallel_sp(gact, p + "fc2.w", resid=x2, bias=f.p(p + "fc2.b"))
         ctx[l] = (x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch)
         return x3
@@ -663,14 +681,7 @@ class GPTStage:
         self._bias_fused.discard(l)
         self._beta = beta
         g3 = tp.all_gather_rows(dx3_c)
-        if self._defer_wg:
-            wt2 = f.wt(p + "fc2.w")
-            du = (G.matmul_nt_dgelu(g3, wt2, u) if wt2 is not None
-                  else G.matmul_nn_dgelu(g3, f.w(p + "fc2.w"), u))
-            self._wg(g3, gact, p + "fc2")
-        else:
-            du = G.linear_backward(g3, f.w(p + "fc2.w"), gact, f.g(p + "fc2.w"), beta, red=red, dgelu_u=u,
-                                   wt=f.wt(p + "fc2.w"))
+        du = self._fc2_bwd(g3, p, u, gact, beta)
         if not fc2b_fused:
             G.colsum(dx3, f.g(p + "fc2.b"), beta, red=red)
         dy2 = self._tp_rs(self._dgrad_wgrad(du, p + "fc1", y2, beta, red, pair=False))

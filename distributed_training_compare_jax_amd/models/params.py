@@ -48,7 +48,7 @@ class ParamSpec:
     shape: Tuple[int, ...]     # full (unsharded) shape
     init: str                  # embed | dense | zeros | ones
     fan_in: int
-    tp: str                    # rep | rows | cols | qkv_rows | head_cols
+    tp: str                    # rep | rows | cols | qkv_rows | head_cols | glu_rows
     layer: int                 # -1 embed, -2 head, else layer index
     mirror: bool               # has a bf16 compute copy (GEMM weight / bias / LN)
     valid_rows: int = -1       # for padded lm_head: rows >= valid_rows are zero
@@ -80,6 +80,10 @@ def layer_param_specs(cfg: ModelConfig, l: int) -> List[ParamSpec]:
     ]
     if cfg.norm == "rmsnorm":  # a scale only: no norm biases
         specs = [s for s in specs if not s.name.endswith((".ln1.b", ".ln2.b"))]
+    if cfg.mlp == "swiglu":  # fc1 = [gate; up]: 2F rows (i.i.d. draws: each half its own lecun-normal fan_in-D kernel)
+        glu = {p + "fc1.w": ParamSpec(p + "fc1.w", (2 * F, D), "dense", D, "glu_rows", l, True),
+               p + "fc1.b": ParamSpec(p + "fc1.b", (2 * F,), "zeros", D, "glu_rows", l, True)}
+        specs = [glu.get(s.name, s) for s in specs]
     return specs
 
 
@@ -198,6 +202,9 @@ def local_shape(spec: ParamSpec, tp_size: int, tp_rank: int = 0) -> Tuple[int, .
     elif spec.tp == "head_cols":
         lo, hi = _head_range(spec, s[1], tp_rank, tp_size)
         s[1] = hi - lo
+    elif spec.tp == "glu_rows":
+        assert s[0] % (2 * tp_size) == 0, f"{spec.name}: gate / up slabs of {s[0] // 2} rows not divisible by tp={tp_size}"
+        s[0] //= tp_size
     elif spec.tp in ("rows", "qkv_rows"):
         assert s[0] % tp_size == 0, f"{spec.name}: dim0 {s[0]} not divisible by tp={tp_size}"
         s[0] //= tp_size
@@ -219,6 +226,9 @@ def shard(spec: ParamSpec, full: torch.Tensor, tp_rank: int, tp_size: int) -> to
     if spec.tp == "head_cols":
         lo, hi = _head_range(spec, full.shape[1], tp_rank, tp_size)
         return full[:, lo:hi].contiguous()
+    if spec.tp == "glu_rows":  # [2F, ...]: the gate and the up slab each split evenly -> [gate_r | up_r]
+        two = full.reshape(2, full.shape[0] // 2, *full.shape[1:])
+        return two.chunk(tp_size, 1)[tp_rank].reshape(-1, *full.shape[1:]).contiguous()
     if spec.tp == "qkv_rows" and spec.kv_heads:  # [(H + 2 Hkv) hd, ...]: each slab's own heads, split evenly
         hd, hq, hk = gqa_slabs(spec, tp_size)
         slabs = full.split([spec.heads * hd, spec.kv_heads * hd, spec.kv_heads * hd], 0)
@@ -240,6 +250,9 @@ def unshard(spec: ParamSpec, shards: List[torch.Tensor]) -> torch.Tensor:
         return torch.cat(shards, 0)
     if spec.tp in ("cols", "head_cols"):
         return torch.cat(shards, 1)
+    if spec.tp == "glu_rows":
+        parts = [s.reshape(2, s.shape[0] // 2, *s.shape[1:]) for s in shards]
+        return torch.cat(parts, 1).reshape(-1, *shards[0].shape[1:])
     if spec.tp == "qkv_rows" and spec.kv_heads:
         hd, hq, hk = gqa_slabs(spec, len(shards))
         parts = [s.split([hq * hd, hk * hd, hk * hd], 0) for s in shards]

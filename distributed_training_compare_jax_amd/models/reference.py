@@ -136,7 +136,12 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
         h = mm(o, p("out.w")) + p("out.b") + r
         r = h
         x = norm(h, f"h.{l}.ln2.g", f"h.{l}.ln2.b")
-        x = _gelu_tanh(mm(x, p("fc1.w")) + p("fc1.b"))
+        x = mm(x, p("fc1.w")) + p("fc1.b")
+        if cfg.mlp == "swiglu":  # fc1 = [gate; up]: silu(gate) * up (ops/swiglu.py)
+            g, u = x.chunk(2, -1)
+            x = F.silu(g) * u
+        else:
+            x = _gelu_tanh(x)
         h = mm(x, p("fc2.w")) + p("fc2.b") + r
     x = norm(h, "lnf.g", "lnf.b")
     V = cfg.vocab_size

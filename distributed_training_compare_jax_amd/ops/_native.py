@@ -121,6 +121,12 @@ def _declare(lib):
         "dtc_add_rmsnorm_fwd_bf16": ([vp, vp, vp, vp, vp, vp, i, i, f, i, vp], i),
         "dtc_rmsnorm_bwd": ([vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, l, i, vp], i),
         "dtc_rmsnorm_bwd_workspace_bytes": ([i, i], l),
+        # SwiGLU (csrc/swiglu.hip): fused fwd x, lda, w, ldb, bias, gu, h, M, F, K, stream; fused bwd dy, lda, w2t, ldb,
+        # gu, dgu, M, F, K, stream; elementwise fwd gu, gu_out, h, mode, M, F, stream; bwd dh, gu, dgu, f32, M, F, stream
+        "dtc_glu_fwd": ([vp, l, vp, l, vp, vp, vp, i, i, i, vp], i),
+        "dtc_glu_bwd": ([vp, l, vp, l, vp, vp, i, i, i, vp], i),
+        "dtc_swiglu_fwd": ([vp, vp, vp, i, i, i, vp], i),
+        "dtc_swiglu_bwd": ([vp, vp, vp, i, i, i, vp], i),
         "dtc_colsum": ([vp, i, i, i, l, vp, f, vp, l, i, vp], i),
         "dtc_gemm_wgrad_split": ([i, i, i, i], i),
         "dtc_gemm_set_n8": ([i], i),

@@ -115,7 +115,7 @@ def head_cost_blocks(cfg, head_speedup: float = 1.7) -> float:
     measured 2.8 in the round-3 kernel table (profiles/r3_gpt2_small_profile_final.md: lm_head
     fwd 713 + dgrad 657 + wgrad 569 + CE 306 us against ~0.8 ms per block)."""
     D, F, V, T = cfg.d_model, cfg.d_ff, cfg.padded_vocab, cfg.max_seq_len
-    block = 6.0 * (4 * D * D + 2 * D * F) + 6.0 * T * D
+    block = 6.0 * (4 * D * D + D * (cfg.fc1_rows + F)) + 6.0 * T * D  # fc1 is 2F rows under mlp: swiglu
     return 6.0 * D * V / block / head_speedup
 
 

@@ -177,6 +177,11 @@ class Engine:
         if model_cfg.norm == "rmsnorm" and train_cfg.fwd_gemm_dtype != "bf16":
             raise ValueError(f"norm=rmsnorm cannot be combined with fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the MXFP8 "
                              "quantiser is fused into the LayerNorm kernel, and the FP8 forwards have not been run with it)")
+        # mlp: swiglu (ops/swiglu.py) runs under every layout, dtype and schedule; what it does not cover is refused
+        # here, by name
+        if model_cfg.mlp == "swiglu" and train_cfg.fwd_gemm_dtype != "bf16":
+            raise ValueError(f"mlp=swiglu cannot be combined with fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the FP8 and "
+                             "MXFP8 forwards fuse their quantiser into the fc1 GELU epilogue)")
         # eval_every: the held-out evaluation (evaluate) -- what it does not cover is refused here, by name
         if train_cfg.eval_every > 0:
             if pp > 1:
@@ -275,7 +280,8 @@ class Engine:
             # Dense / lm_head dgrads as NT GEMMs on a transposed bf16 weight copy (buffers.enable_transposed)
             # (fc2's dgrad + dGELU runs NN on the row-major weight: level with the NT form on a mirror,
             # profiles/r5_gemm8r.md, so fc2 needs no transposed copy)
-            dense = ["fc1", "qkv", "out"]
+            # (mlp: swiglu: its fused fc2 dgrad, csrc/swiglu.hip glu_bwd_kernel, is an NT kernel on the mirror)
+            dense = ["fc1", "qkv", "out"] + (["fc2"] if model_cfg.mlp == "swiglu" else [])
             head = ["lm_head.w"] if os.environ.get("DTC_DGRAD_NT_HEAD", "1") == "1" else []
             self.flat.enable_transposed([f"h.{l}.{n}.w" for l in self.layout.layers for n in dense] + head)
         self.flat.init_canonical(train_cfg.seed)
@@ -639,6 +645,8 @@ class Engine:
         tokens = (self.mb_rows if self.grad_accum > 1 else self.b_local) * self.T  # alive at once
         esize = 2 if self.act_dtype == torch.bfloat16 else 4
         D, F = mc.d_model, mc.d_ff
+        if mc.mlp == "swiglu":  # dgu [2F] and h [F] in place of du [F] and gelu(u) [F]
+            F = 3 * F // 2
         per_layer = (8 * D + 2 * F) * tokens * esize
         env = os.environ.get("DTC_WGRAD_MEM_MB")
         if env is not None:
@@ -671,7 +679,7 @@ class Engine:
         one-sequence microbatch -- the messages are NOT negligible).  Deterministic, identical on every rank."""
         mc, T, rows = self.mcfg, self.T, self.mb_rows
         D, F = mc.d_model, mc.d_ff
-        block_s = 6.0 * (4 * D * D + 2 * D * F + T * D) * rows * T / 600e12
+        block_s = 6.0 * (4 * D * D + D * (mc.fc1_rows + F) + T * D) * rows * T / 600e12
         esz = 2 if getattr(self, "pp_bf16", False) else 4
         fb = rows * T * D * esz / 50e9 / block_s
         return {"f": fb, "b": fb, "s": 1e-5 / block_s}

@@ -52,7 +52,7 @@ def save(eng, output_dir: str, step: int):
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
                 vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab),
                 n_kv_heads=int(eng.mcfg.kv_heads), pos_emb=eng.mcfg.pos_emb, rope_theta=float(eng.mcfg.rope_theta),
-                norm=eng.mcfg.norm)
+                norm=eng.mcfg.norm, mlp=eng.mcfg.mlp)
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
         json.dump(meta, fh)
 
@@ -147,6 +147,11 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
     norm_ck, norm_now = m0.get("norm", "layernorm"), eng.mcfg.norm
     if norm_ck != norm_now:
         raise ValueError(f"checkpoint was written with norm={norm_ck!r}, this run has norm={norm_now!r}: resume with "
+                         "the value that wrote it")
+    # the MLP decides the shape and the meaning of fc1 (before the field: gelu)
+    mlp_ck, mlp_now = m0.get("mlp", "gelu"), eng.mcfg.mlp
+    if mlp_ck != mlp_now:
+        raise ValueError(f"checkpoint was written with mlp={mlp_ck!r}, this run has mlp={mlp_now!r}: resume with "
                          "the value that wrote it")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
