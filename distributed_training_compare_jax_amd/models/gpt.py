@@ -14,6 +14,13 @@ points per block Megatron-style TP needs, and the whole step is a static sequenc
 kernel launches that can be captured into hipGraphs.  Numerical equivalence to the
 autograd oracle (``models/reference.py``) is tested in ``tests/test_model.py``.
 
+The block's op sequence (norm, qkv, rope, attention, out_proj + residual + norm, fc1, fc2 + residual) is written
+once, in ``GPTStage.block_forward`` / ``block_backward``, for every forward precision (bf16, FP8, MXFP8) and layout
+(one rank, TP with all-reduces, TP with sequence parallelism).  What differs sits in small methods at the site where
+it differs: ``_norm`` / ``_add_norm`` (the norm kind, and the MXFP8 form of its output), ``_linear`` / ``_fc1`` (the
+operand precision), ``_row_resid_norm`` (how a row-parallel GEMM, its residual add and the next norm are combined),
+``_rows`` / ``_tp_sum`` (sequence parallelism's all-gather and reduce-scatter).  A new block feature goes there once.
+
 Dtypes: residual stream fp32; GEMM operands in the compute dtype (bf16 on MI355X, fp32
 on the CPU oracle path); all accumulation fp32; grads fp32.
 """
@@ -22,7 +29,7 @@ from __future__ import annotations
 
 import contextlib
 from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -114,6 +121,27 @@ class StageLayout:
     # (part, parts): lm_head + CE split by vocab over the last `parts` pipeline stages (pp_head_split);
     # part 0 also holds the final LayerNorm
     head_part: Tuple[int, int] = (0, 1)
+
+
+class BlockCtx(NamedTuple):
+    """What ``block_forward`` keeps of layer l for ``block_backward`` (``ctx[l]``).  ``y1`` / ``y2`` / ``qkv`` / ``o`` /
+    ``u`` / ``gact`` hold the rows the GEMMs read (all of them under sequence parallelism), ``x`` / ``x2`` and the
+    norm statistics this rank's rows; ``mu1`` / ``mu2`` are None under ``rmsnorm``."""
+
+    x: torch.Tensor
+    y1: torch.Tensor
+    mu1: Optional[torch.Tensor]
+    rs1: torch.Tensor
+    qkv: torch.Tensor
+    o: torch.Tensor
+    lse: torch.Tensor
+    x2: torch.Tensor
+    y2: torch.Tensor
+    mu2: Optional[torch.Tensor]
+    rs2: torch.Tensor
+    u: torch.Tensor
+    gact: torch.Tensor
+    batch: int
 
 
 class GPTStage:
@@ -337,28 +365,61 @@ class GPTStage:
 
     def _norm(self, x: torch.Tensor, ln: str):
         """Norm ``ln`` (``h.<l>.ln1`` / ``h.<l>.ln2`` / ``lnf``) of the fp32 rows ``x`` by ``cfg.norm`` -> ``(y, mean,
-        rstd)``, what the backward gets back; ``mean`` is None under ``rmsnorm`` (it has none)."""
+        rstd, yq)``: what the backward gets back (``mean`` is None under ``rmsnorm``, it has none) and the MXFP8 form
+        of ``y`` where the norm pass wrote it (the MXFP8 forward; not ``lnf``, which feeds the bf16 lm_head), else None."""
         f = self.flat
         if self.rms:
             y, rs = RN.rmsnorm_fwd(x, f.p(ln + ".g"), self.eps, self.act_dtype)
-            return y, None, rs
-        return LN.layernorm_fwd(x, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
+            return y, None, rs, None
+        if self.mx and ln != "lnf":
+            pre, yq = MX.layernorm_fwd_mx(x, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
+            return (*pre, yq)
+        return (*LN.layernorm_fwd(x, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype), None)
 
     def _add_norm(self, d: torch.Tensor, resid: torch.Tensor, ln: str):
-        """``x = d + resid`` and :meth:`_norm` of it in one pass -> ``(x, (y, mean, rstd))``."""
+        """``x = d + resid`` and :meth:`_norm` of it in one pass -> ``(x, (y, mean, rstd, yq))``."""
         f = self.flat
         if self.rms:
             x, (y, rs) = RN.add_rmsnorm_fwd(d, resid, f.p(ln + ".g"), self.eps, self.act_dtype)
-            return x, (y, None, rs)
-        return LN.add_layernorm_fwd(d, resid, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
+            return x, (y, None, rs, None)
+        if self.mx and ln != "lnf":
+            x, pre, yq = MX.add_layernorm_fwd_mx(d, resid, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
+            return x, (*pre, yq)
+        x, pre = LN.add_layernorm_fwd(d, resid, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.act_dtype)
+        return x, (*pre, None)
 
-    def _fc1(self, y2: torch.Tensor, p: str):
-        """The first half of the MLP of block ``p`` by ``cfg.mlp`` -> ``(saved, act)``: the fc2 input ``act`` and what
-        :meth:`_fc2_bwd` gets back (``gelu'(u)``, or the gated pre-activations ``g | u`` under ``swiglu``)."""
+    def _quant(self, a: torch.Tensor, aq=None):
+        """The operand form of ``a`` for the forward GEMM precision: ``aq`` if its producer wrote one, else ``a``
+        quantised now (FP8: the scale of the current tensor; MXFP8: the one-pass quantiser); None under bf16."""
+        if aq is not None or not (self.fp8 or self.mx):
+            return aq
+        return F8.quant_e4m3(a) if self.fp8 else MX.quant_mxfp8(a)
+
+    def _linear(self, a: torch.Tensor, aq, dense: str, out_dtype: Optional[torch.dtype] = None):
+        """``a·Wᵀ + b`` of Dense ``dense`` in the forward GEMM precision (``aq``: :meth:`_quant`); ``out_dtype``
+        defaults to the compute dtype.  The column-parallel GEMMs (qkv; fc1 is :meth:`_fc1`) and the row-parallel
+        ones whose residual the norm pass adds."""
+        f, b = self.flat, self.flat.p(dense + ".b")
+        if self.fp8:
+            return F8.linear_fp8(self._quant(a, aq), f.w8(dense + ".w"), b, out_dtype=out_dtype or self.act_dtype)
+        if self.mx:
+            return MX.linear_mxfp8(self._quant(a, aq), f.wmx(dense + ".w"), b, out_dtype=out_dtype or self.act_dtype)
+        return G.linear(a, f.w(dense + ".w"), b, out_dtype=out_dtype)
+
+    def _fc1(self, y2: torch.Tensor, y2q, p: str):
+        """The first half of the MLP of block ``p`` by ``cfg.mlp`` -> ``(saved, act, actq)``: the fc2 input ``act``
+        (``actq``: its quantised form under the FP8 / MXFP8 forward, else None) and what :meth:`_fc2_bwd` gets back
+        (``gelu'(u)``, or the gated pre-activations ``g | u`` under ``swiglu``)."""
         f = self.flat
         if self.glu:
-            return SW.swiglu_fc1(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))
-        return G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b"))  # u = gelu'(pre-activation)
+            return (*SW.swiglu_fc1(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b")), None)
+        if self.fp8:
+            u, gact = F8.linear_gelu_fp8(self._quant(y2, y2q), f.w8(p + "fc1.w"), f.p(p + "fc1.b"), out_dtype=self.act_dtype)
+            return u, gact, F8.quant_e4m3(gact)
+        if self.mx:  # the GELU epilogue writes the MX form of gelu(u) itself
+            return MX.linear_gelu_mxfp8(self._quant(y2, y2q), f.wmx(p + "fc1.w"), f.p(p + "fc1.b"),
+                                        out_dtype=self.act_dtype, quant_out=True)
+        return (*G.linear_gelu(y2, f.w(p + "fc1.w"), f.p(p + "fc1.b")), None)  # u = gelu'(pre-activation)
 
     def _fc2_bwd(self, dy: torch.Tensor, p: str, saved: torch.Tensor, act: torch.Tensor, beta: float):
         """fc2's dgrad through the activation backward -> the gradient of the fc1 output, and fc2's weight gradient
@@ -460,131 +521,92 @@ class GPTStage:
         """dtype of the out_proj / fc2 outputs the LayerNorm pass adds to the residual (DTC_FWD_BF16)."""
         return torch.bfloat16 if _FWD_BF16 and self.act_dtype == torch.bfloat16 else torch.float32
 
-    def _block_forward_mx(self, l: int, x: torch.Tensor, batch: int, ctx: Dict) -> torch.Tensor:
-        """:meth:`block_forward` with the four layer GEMMs on MXFP8 operands (enable_mxfp8_forward; tp == 1, no
-        LayerNorm-GEMM fusion).  Every LayerNorm that feeds a layer GEMM returns the MX form of its output with it,
-        and hands it on to the next layer beside ``ctx[("ln1", l + 1)]``; ``lnf`` feeds the bf16 lm_head and has
-        none.  ``ctx[l]`` holds the same tensors as the bf16 forward's."""
-        self._await_params(l)
-        f, p = self.flat, f"h.{l}."
-        T = x.shape[0] // batch
-        act = self.act_dtype
-        pre = ctx.pop(("ln1", l), None)  # LN1 (and its MX form) already produced by the previous layer
-        y1q = ctx.pop(("ln1_mx", l), None)
-        if pre is None:
-            pre, y1q = MX.layernorm_fwd_mx(x, f.p(p + "ln1.g"), f.p(p + "ln1.b"), self.eps, act)
-        y1, mu1, rs1 = pre
-        if y1q is None:
-            y1q = MX.quant_mxfp8(y1)
-        qkv = MX.linear_mxfp8(y1q, f.wmx(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=act)
-        self._rope(qkv, batch)
-        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
-        o = o.view(batch * T, -1)
-        oq = MX.quant_mxfp8(o)
-        if _ADD_LN:  # residual add in the LayerNorm pass, as block_forward
-            br = MX.linear_mxfp8(oq, f.wmx(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype)
-            x2, (y2, mu2, rs2), y2q = MX.add_layernorm_fwd_mx(br, x, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, act)
+    def _rows(self, t: torch.Tensor) -> torch.Tensor:
+        """The rows the layer GEMMs read: under sequence parallelism every rank's rows of ``t`` (the residual
+        stream and the norms hold ``rows / tp`` of them), else ``t`` itself."""
+        return self.tp.all_gather_rows(t) if self.sp else t
+
+    def _row_resid_norm(self, a, aq, dense: str, resid, ln: Optional[str], site: int, defer_norm: bool):
+        """The row-parallel Dense ``dense`` (out_proj / fc2) on ``a`` (``aq``: :meth:`_quant`) with its residual add,
+        and the norm ``ln`` that reads the result -> ``(x, norm result)``, ``x = resid + b + Σ_tp a·Wᵀ``.  ``ln`` None:
+        nothing on this stage reads ``x`` (fc2 of the last layer without the head).  ``defer_norm`` (fc2): the norm
+        runs here only where it shares a pass with the add, and is otherwise left to its reader (the next block, the
+        head) -> ``(x, None)``.  ``site``: :meth:`_ln_site` of the GEMM-fused LayerNorm.
+
+        One choice for both sites.  ``tp_bf16`` and ``sp`` imply tp > 1 (train/engine.py, enable_sequence_parallel)
+        and the LayerNorm fusion tp == 1, so the conditions exclude each other and their order is free."""
+        f, tp = self.flat, self.tp
+        w, b = dense + ".w", f.p(dense + ".b")
+        aq = self._quant(a, aq)
+        if self._fuse_fwd and ln is not None:
+            x, pre = LF.linear_resid_ln(a, f.w(w), b, resid, f.p(ln + ".g"), f.p(ln + ".b"), self.eps, self.ln_sync, site)
+            return x, (*pre, None)
+        if tp.size == 1 and _ADD_LN and ln is not None:
+            # residual add in the norm pass (the GEMM stores a·Wᵀ + b; its epilogue skips the fp32 residual
+            # read) -- same fp32 arithmetic, (acc + b) + x
+            return self._add_norm(self._linear(a, aq, dense, self._branch_dtype), resid, ln)
+        if self.sp:
+            x = self._row_parallel_sp(a, w, resid=resid, bias=b)
+        elif self.tp_bf16:
+            x = self._row_parallel(a, w, resid=resid, bias=b)
         else:
-            x2 = MX.linear_resid_mxfp8(oq, f.wmx(p + "out.w"), f.p(p + "out.b"), x)
-            (y2, mu2, rs2), y2q = MX.layernorm_fwd_mx(x2, f.p(p + "ln2.g"), f.p(p + "ln2.b"), self.eps, act)
-        u, gact, gq = MX.linear_gelu_mxfp8(y2q, f.wmx(p + "fc1.w"), f.p(p + "fc1.b"), out_dtype=act, quant_out=True)
-        nxt = f"h.{l + 1}.ln1" if (l + 1) in self.layout.layers else ("lnf" if self.layout.has_head else None)
-        if _ADD_LN and nxt is not None:
-            br = MX.linear_mxfp8(gq, f.wmx(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype)
-            if nxt == "lnf":
-                x3, ctx["lnf_pre"] = self._add_norm(br, x2, "lnf")
+            lead = tp.rank == 0  # row-parallel bias + residual are added by exactly one TP rank
+            if self.fp8:
+                x = F8.linear_resid_fp8(aq, f.w8(w), b, resid)
+            elif self.mx:
+                x = MX.linear_resid_mxfp8(aq, f.wmx(w), b, resid)
             else:
-                x3, ctx[("ln1", l + 1)], ctx[("ln1_mx", l + 1)] = MX.add_layernorm_fwd_mx(
-                    br, x2, f.p(nxt + ".g"), f.p(nxt + ".b"), self.eps, act)
-        else:
-            x3 = MX.linear_resid_mxfp8(gq, f.wmx(p + "fc2.w"), f.p(p + "fc2.b"), x2)
-        ctx[l] = (x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch)
-        return x3
+                x = G.linear_resid(a, f.w(w), b if lead else None, resid if lead else None)
+            tp.all_reduce_(x)
+        return x, (None if defer_norm else self._norm(x, ln))
 
     def block_forward(self, l: int, x: torch.Tensor, batch: int, ctx: Dict) -> torch.Tensor:
-        if self.sp:
-            return self._block_forward_sp(l, x, batch, ctx)
-        if self.mx:
-            return self._block_forward_mx(l, x, batch, ctx)
+        """One pre-norm block on the fp32 residual rows ``x`` (this rank's under sequence parallelism), every
+        precision and layout: what differs between them sits in the helpers (:meth:`_norm`, :meth:`_linear`,
+        :meth:`_fc1`, :meth:`_row_resid_norm`, :meth:`_rows`).  ``ctx[l]`` (:class:`BlockCtx`) holds the same
+        unquantised tensors under every forward precision."""
         self._await_params(l)
-        f, p = self.flat, f"h.{l}."
-        tp = self.tp
-        lead = tp.rank == 0  # row-parallel bias + residual are added by exactly one TP rank
-        T = x.shape[0] // batch
-        pre = ctx.pop(("ln1", l), None)  # LN1 already produced by the previous layer's fc2 GEMM
-        if pre is None:
-            pre = self._norm(x, p + "ln1")
-        y1, mu1, rs1 = pre
-        fp8 = self.fp8  # the four layer GEMMs on e4m3 operands (enable_fp8_forward); ctx keeps the same tensors
-        if fp8:
-            qkv = F8.linear_fp8(F8.quant_e4m3(y1), f.w8(p + "qkv.w"), f.p(p + "qkv.b"), out_dtype=self.act_dtype)
-        else:
-            qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
+        p = f"h.{l}."
+        pre = ctx.pop(("ln1", l), None)  # ln1 already produced by the previous layer's fc2 site
+        y1l, mu1, rs1, y1q = pre if pre is not None else self._norm(x, p + "ln1")
+        y1 = self._rows(y1l)
+        T = y1.shape[0] // batch
+        qkv = self._linear(y1, y1q, p + "qkv")
         self._rope(qkv, batch)
         o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
         o = o.view(batch * T, -1)
-        oq = F8.quant_e4m3(o) if fp8 else None
-        if self._fuse_fwd:
-            x2, (y2, mu2, rs2) = LF.linear_resid_ln(o, f.w(p + "out.w"), f.p(p + "out.b"), x, f.p(p + "ln2.g"),
-                                                    f.p(p + "ln2.b"), self.eps, self.ln_sync, self._ln_site(l, 0, False))
-        elif self.tp_bf16:
-            x2 = self._row_parallel(o, p + "out.w", resid=x, bias=f.p(p + "out.b"))
-            y2, mu2, rs2 = self._norm(x2, p + "ln2")
-        elif tp.size == 1 and _ADD_LN:
-            # residual add in the LayerNorm pass (the GEMM stores o·Wᵀ + b; its epilogue skips the fp32
-            # residual read) -- same fp32 arithmetic, (acc + b) + x
-            br = (F8.linear_fp8(oq, f.w8(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype) if fp8 else
-                  G.linear(o, f.w(p + "out.w"), f.p(p + "out.b"), out_dtype=self._branch_dtype))
-            x2, (y2, mu2, rs2) = self._add_norm(br, x, p + "ln2")
-        else:
-            if fp8:
-                x2 = F8.linear_resid_fp8(oq, f.w8(p + "out.w"), f.p(p + "out.b"), x)
-            else:
-                x2 = G.linear_resid(o, f.w(p + "out.w"), f.p(p + "out.b") if lead else None, x if lead else None)
-            tp.all_reduce_(x2)
-            y2, mu2, rs2 = self._norm(x2, p + "ln2")
-        if fp8:
-            u, gact = F8.linear_gelu_fp8(F8.quant_e4m3(y2), f.w8(p + "fc1.w"), f.p(p + "fc1.b"), out_dtype=self.act_dtype)
-            gq = F8.quant_e4m3(gact)
-        else:
-            u, gact = self._fc1(y2, p)
-        # the LayerNorm that reads x3: the next layer's ln1, or the final one after the last layer
+        x2, (y2l, mu2, rs2, y2q) = self._row_resid_norm(o, None, p + "out", x, p + "ln2", self._ln_site(l, 0, False),
+                                                        defer_norm=False)
+        y2 = self._rows(y2l)
+        u, gact, gq = self._fc1(y2, y2q, p)
+        # the norm that reads x3: the next layer's ln1, or the final one after the last layer
         nxt = f"h.{l + 1}.ln1" if (l + 1) in self.layout.layers else ("lnf" if self.layout.has_head else None)
-        if self._fuse_fwd and nxt is not None:
-            x3, pre_next = LF.linear_resid_ln(gact, f.w(p + "fc2.w"), f.p(p + "fc2.b"), x2, f.p(nxt + ".g"),
-                                              f.p(nxt + ".b"), self.eps, self.ln_sync, self._ln_site(l, 1, False))
+        x3, pre_next = self._row_resid_norm(gact, gq, p + "fc2", x2, nxt, self._ln_site(l, 1, False), defer_norm=True)
+        if pre_next is not None:
             ctx[("ln1", l + 1) if nxt != "lnf" else "lnf_pre"] = pre_next
-        elif tp.size == 1 and _ADD_LN and nxt is not None and not self.tp_bf16:
-            br = (F8.linear_fp8(gq, f.w8(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype) if fp8 else
-                  G.linear(gact, f.w(p + "fc2.w"), f.p(p + "fc2.b"), out_dtype=self._branch_dtype))
-            x3, pre_next = self._add_norm(br, x2, nxt)
-            ctx[("ln1", l + 1) if nxt != "lnf" else "lnf_pre"] = pre_next
-        elif self.tp_bf16:
-            x3 = self._row_parallel(gact, p + "fc2.w", resid=x2, bias=f.p(p + "fc2.b"))
-        elif fp8:
-            x3 = F8.linear_resid_fp8(gq, f.w8(p + "fc2.w"), f.p(p + "fc2.b"), x2)
-        else:
-            x3 = G.linear_resid(gact, f.w(p + "fc2.w"), f.p(p + "fc2.b") if lead else None, x2 if lead else None)
-            tp.all_reduce_(x3)
-        ctx[l] = (x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch)
+        ctx[l] = BlockCtx(x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch)
         return x3
 
     def block_backward(self, l: int, ctx: Dict, dx3: torch.Tensor, dx3_c: torch.Tensor, beta: float, dx_hook=None):
         """dx3 fp32 (and its compute-dtype copy) → (dx, dx_c) wrt the block input.  ``dx_hook(dx, dx_c)``
         (optional) is called as soon as dx is final, before the layer's remaining weight-gradient
-        work (the DP embedding gather starts there, under that work)."""
-        if self.sp:
-            return self._block_backward_sp(l, ctx, dx3, dx3_c, beta, dx_hook)
+        work (the DP embedding gather starts there, under that work).
+
+        Under sequence parallelism dx3 / dx are this rank's rows: the residual gradient is all-gathered in the
+        compute dtype for the GEMMs (:meth:`_rows`), their input-gradient partials are reduce-scattered
+        (:meth:`_tp_sum`), and the norm and row-parallel-bias grads come out as partials over the own rows
+        (summed by :meth:`_sp_sum`)."""
         f, p = self.flat, f"h.{l}."
-        x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch = ctx.pop(l)
-        T = x.shape[0] // batch
+        c: BlockCtx = ctx.pop(l)
+        batch = c.batch
+        T = c.y1.shape[0] // batch
         red = self.red
         # fc2.b's gradient = Σ_rows dx3 was already emitted by the LayerNorm backward that produced
         # dx3 (lnf or the next block's ln1) unless dx3 arrived from another pipeline stage
         fc2b_fused = l in self._bias_fused
         self._bias_fused.discard(l)
         self._beta = beta
-        du = self._fc2_bwd(dx3_c, p, u, gact, beta)
+        du = self._fc2_bwd(self._rows(dx3_c), p, c.u, c.gact, beta)
         if not fc2b_fused:
             G.colsum(dx3, f.g(p + "fc2.b"), beta, red=red)
         # paired launches measured per Dense (in-step, us): fc2 44.1 vs 46.8 and qkv 35.6 vs 38.1
@@ -593,43 +615,45 @@ class GPTStage:
         if self._fuse_bwd and wt1 is not None:
             # fc1 dgrad with the LN2 backward in its epilogue (+ out_proj.b's gradient), then fc1's
             # weight gradient
-            dx2, dx2_c = LF.dgrad_ln_bwd(du, wt1, x2, f.p(p + "ln2.g"), mu2, rs2, dx3, f.g(p + "ln2.g"),
+            dx2, dx2_c = LF.dgrad_ln_bwd(du, wt1, c.x2, f.p(p + "ln2.g"), c.mu2, c.rs2, dx3, f.g(p + "ln2.g"),
                                          f.g(p + "ln2.b"), beta, dbias=f.g(p + "out.b"), red=red,
                                          sync=self.ln_sync, site=self._ln_site(l, 0, True))
-            self._wg(du, y2, p + "fc1", bias=True)
+            self._wg(du, c.y2, p + "fc1", bias=True)
         else:
-            dy2 = self._tp_reduce(self._dgrad_wgrad(du, p + "fc1", y2, beta, red, pair=False))
-            dx2, dx2_c = self._ln_bwd(dy2, x2, p + "ln2", mu2, rs2, dx3, beta, bias_grad=p + "out.b")
+            dy2 = self._tp_sum(self._dgrad_wgrad(du, p + "fc1", c.y2, beta, red, pair=False))
+            dx2, dx2_c = self._ln_bwd(dy2, c.x2, p + "ln2", c.mu2, c.rs2, dx3, beta, bias_grad=p + "out.b")
+        # out_proj: its input gradient stays on this rank's heads (no TP sum) in the compute dtype, and it has no
+        # bias gradient here (out.b's comes from the ln2 backward above) -- not _dgrad_wgrad's fp32 partial
+        g2 = self._rows(dx2_c)
         wto = f.wt(p + "out.w")
         if wto is not None:  # NT dgrad on the transposed weight, then the weight gradient
-            do = G.linear(dx2_c, wto)
-            self._wg(dx2_c, o, p + "out")
+            do = G.linear(g2, wto)
+            self._wg(g2, c.o, p + "out")
         elif self._defer_wg:
-            do = G.matmul_nn(dx2_c, f.w(p + "out.w"), out_dtype=self.act_dtype)
-            self._wg(dx2_c, o, p + "out")
+            do = G.matmul_nn(g2, f.w(p + "out.w"), out_dtype=self.act_dtype)
+            self._wg(g2, c.o, p + "out")
         else:
-            do = G.linear_backward(dx2_c, f.w(p + "out.w"), o, f.g(p + "out.w"), beta, red=red,
+            do = G.linear_backward(g2, f.w(p + "out.w"), c.o, f.g(p + "out.w"), beta, red=red,
                                    out_dtype=self.act_dtype, pair=False)
-        dqkv = A.attn_bwd(qkv.view(batch, T, -1), o.view(batch, T, -1), lse, do.view(batch, T, -1),
+        dqkv = A.attn_bwd(c.qkv.view(batch, T, -1), c.o.view(batch, T, -1), c.lse, do.view(batch, T, -1),
                           self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local).view(batch * T, -1)
         self._rope(dqkv, batch, inverse=True)
         wtq = f.wt(p + "qkv.w")
         if self._fuse_bwd and wtq is not None:
             bg = self._prev_fc2b(l)
-            out = LF.dgrad_ln_bwd(dqkv, wtq, x, f.p(p + "ln1.g"), mu1, rs1, dx2, f.g(p + "ln1.g"), f.g(p + "ln1.b"),
+            out = LF.dgrad_ln_bwd(dqkv, wtq, c.x, f.p(p + "ln1.g"), c.mu1, c.rs1, dx2, f.g(p + "ln1.g"), f.g(p + "ln1.b"),
                                   beta, dbias=None if bg is None else f.g(bg), red=red, sync=self.ln_sync,
                                   site=self._ln_site(l, 1, True))
             if dx_hook is not None:
                 dx_hook(*out)
-            self._wg(dqkv, y1, p + "qkv", bias=True)
+            self._wg(dqkv, c.y1, p + "qkv", bias=True)
             return out
-        dy1 = self._tp_reduce(self._dgrad_wgrad(dqkv, p + "qkv", y1, beta, red, pair=True))
-        out = self._ln_bwd(dy1, x, p + "ln1", mu1, rs1, dx2, beta, bias_grad=self._prev_fc2b(l))
+        dy1 = self._tp_sum(self._dgrad_wgrad(dqkv, p + "qkv", c.y1, beta, red, pair=True))
+        out = self._ln_bwd(dy1, c.x, p + "ln1", c.mu1, c.rs1, dx2, beta, bias_grad=self._prev_fc2b(l))
         if dx_hook is not None:
             dx_hook(*out)
         return out
 
-    # ------------------------------------------------------------------ sequence-parallel block
     def _row_parallel_sp(self, a, wname: str, resid, bias):
         """resid + bias + Σ_tp a·Wᵀ on this rank's rows (reduce-scatter); the partial is bf16 under
         ``tp_bf16``, else fp32, written by the GEMM straight into the P2P buffer when that path takes it."""
@@ -647,64 +671,6 @@ class GPTStage:
         if isinstance(d, _Staged):
             return self.tp.reduce_scatter_staged(d.rows, d.cols, torch.bfloat16, device=d.device)
         return self.tp.reduce_scatter_rows(d)
-
-    def _block_forward_sp(self, l: int, x: torch.Tensor, batch: int, ctx: Dict) -> torch.Tensor:
-        self._await_params(l)
-        f, p, tp = self.flat, f"h.{l}.", self.tp
-        rows = x.shape[0] * tp.size
-        T = rows // batch
-        y1l, mu1, rs1 = self._norm(x, p + "ln1")
-        y1 = tp.all_gather_rows(y1l)
-        qkv = G.linear(y1, f.w(p + "qkv.w"), f.p(p + "qkv.b"))
-        self._rope(qkv, batch)
-        o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
-        o = o.view(rows, -1)
-        x2 = self._row_parallel_sp(o, p + "out.w", resid=x, bias=f.p(p + "out.b"))
-        y2l, mu2, rs2 = self._norm(x2, p + "ln2")
-        y2 = tp.all_gather_rows(y2l)
-        u, gact = self._fc1(y2, p)
-        x3 = self._row_parallel_sp(gact, p + "fc2.w", resid=x2, bias=f.p(p + "fc2.b"))
-        ctx[l] = (x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch)
-        return x3
-
-    def _block_backward_sp(self, l: int, ctx: Dict, dx3: torch.Tensor, dx3_c: torch.Tensor, beta: float,
-                           dx_hook=None):
-        """dx3 (fp32, own rows) → (dx, dx_c) on the own rows.  The residual gradient is all-gathered in the
-        compute dtype for the GEMMs, their input-gradient partials are reduce-scattered; the LayerNorm and
-        row-parallel-bias grads come out as partials over the own rows (summed by :meth:`_sp_sum`)."""
-        f, p, tp = self.flat, f"h.{l}.", self.tp
-        x, y1, mu1, rs1, qkv, o, lse, x2, y2, mu2, rs2, u, gact, batch = ctx.pop(l)
-        rows = y1.shape[0]
-        T = rows // batch
-        red = self.red
-        fc2b_fused = l in self._bias_fused
-        self._bias_fused.discard(l)
-        self._beta = beta
-        g3 = tp.all_gather_rows(dx3_c)
-        du = self._fc2_bwd(g3, p, u, gact, beta)
-        if not fc2b_fused:
-            G.colsum(dx3, f.g(p + "fc2.b"), beta, red=red)
-        dy2 = self._tp_rs(self._dgrad_wgrad(du, p + "fc1", y2, beta, red, pair=False))
-        dx2, dx2_c = self._ln_bwd(dy2, x2, p + "ln2", mu2, rs2, dx3, beta, bias_grad=p + "out.b")
-        g2 = tp.all_gather_rows(dx2_c)
-        wto = f.wt(p + "out.w")
-        if wto is not None:
-            do = G.linear(g2, wto)
-            self._wg(g2, o, p + "out")
-        elif self._defer_wg:
-            do = G.matmul_nn(g2, f.w(p + "out.w"), out_dtype=self.act_dtype)
-            self._wg(g2, o, p + "out")
-        else:
-            do = G.linear_backward(g2, f.w(p + "out.w"), o, f.g(p + "out.w"), beta, red=red,
-                                   out_dtype=self.act_dtype, pair=False)
-        dqkv = A.attn_bwd(qkv.view(batch, T, -1), o.view(batch, T, -1), lse, do.view(batch, T, -1),
-                          self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local).view(rows, -1)
-        self._rope(dqkv, batch, inverse=True)
-        dy1 = self._tp_rs(self._dgrad_wgrad(dqkv, p + "qkv", y1, beta, red, pair=True))
-        out = self._ln_bwd(dy1, x, p + "ln1", mu1, rs1, dx2, beta, bias_grad=self._prev_fc2b(l))
-        if dx_hook is not None:
-            dx_hook(*out)
-        return out
 
     def _row_parallel(self, a, wname: str, resid, bias):
         """fp32 ``resid + bias + Σ_tp a·Wᵀ`` with a bf16 partial (``tp_bf16``): the GEMM writes the partial
@@ -808,7 +774,7 @@ class GPTStage:
         self._await_params("head")
         f = self.flat
         pre = ctx.pop("lnf_pre", None)  # produced by the last layer's fc2 GEMM (fused LayerNorm)
-        yf, muf, rsf = pre if pre is not None else self._norm(x, "lnf")
+        yf, muf, rsf, _ = pre if pre is not None else self._norm(x, "lnf")
         if self.sp:
             yf = self.tp.all_gather_rows(yf)  # the vocab-parallel lm_head reads every row
         lab = labels.reshape(-1)
@@ -888,7 +854,7 @@ class GPTStage:
         """Part 0: the final LayerNorm of the stage output -- the message to part 1 (compute dtype)."""
         f = self.flat
         self._await_params("head")
-        yf, muf, rsf = self._norm(x, "lnf")
+        yf, muf, rsf, _ = self._norm(x, "lnf")
         ctx["head_yf"] = (x, yf, muf, rsf)
         return yf
 
@@ -955,7 +921,7 @@ class GPTStage:
             G.colsum(cp, gb[c0:c0 + vc], beta, red=red)
             self.flush_reductions()  # this chunk's split-K slabs: the reducer arena is reused by the next
             del logits, dl, cp
-        dyf = self._head_dx(dyf)
+        dyf = self._tp_sum(dyf)
         last = self.layout.layers[-1] + 1 if len(self.layout.layers) else None
         out = self._ln_bwd(dyf, x, "lnf", muf, rsf, None, beta,
                            bias_grad=None if last is None else self._prev_fc2b(last))
@@ -963,12 +929,13 @@ class GPTStage:
         self._sp_sum(["head"])
         return out
 
-    def _head_dx(self, dyf):
-        """The lm_head input gradient summed over the vocab shards: all-reduced, or under sequence
-        parallelism reduce-scattered to the own rows (``dyf`` a tensor or a :class:`_Staged` bf16 partial)."""
+    def _tp_sum(self, d):
+        """An input-gradient partial (of a column-parallel Dense, or of the lm_head's vocab shard) summed over the
+        TP group: all-reduced, or under sequence parallelism reduce-scattered to the own rows (``d`` a tensor or a
+        :class:`_Staged` bf16 partial)."""
         if self.sp:
-            return self._tp_rs(dyf)
-        return self._tp_reduce(dyf)
+            return self._tp_rs(d)
+        return self._tp_reduce(d)
 
     def _head_dgrad(self, dlogits, wt):
         """dlogits·W, the lm_head input gradient of this rank's vocab shard.  Under ``tp_bf16`` (tp > 1, no
@@ -1031,7 +998,7 @@ class GPTStage:
                 return dyf, None
             dyf.add_(extra_dyf)
         else:
-            dyf = self._head_dx(dyf)
+            dyf = self._tp_sum(dyf)
         last = self.layout.layers[-1] + 1 if len(self.layout.layers) else None
         out = self._ln_bwd(dyf, x, "lnf", muf, rsf, None, beta,
                            bias_grad=None if last is None else self._prev_fc2b(last))

@@ -140,23 +140,32 @@ def test_zero1_replicas_identical():
 HEADS12 = {"d_model": 96, "n_heads": 12, "d_ff": 256, "n_layers": 2}
 
 
+# the newer model options together (grouped-query attention, rotary positions, RMSNorm, SwiGLU) under tensor
+# parallelism: whole groups per rank (2 K/V heads on 2 ranks), the gated fc1's two slabs split by rank
+GQA_ROPE_RMS_GLU = {"d_model": 64, "n_heads": 4, "n_kv_heads": 2, "d_ff": 192, "n_layers": 2, "norm": "rmsnorm",
+                    "mlp": "swiglu", "pos_emb": "rope"}
+
+
 @pytest.mark.slow
-@pytest.mark.parametrize("parallel,world,kw", [
-    ("tp", 8, {}),
-    ("dp", 8, {"tp": 4}),  # dp2 x tp4: 3 heads per rank
-    ("tp", 8, {"tp_sequence_parallel": True, "batch": 8}),  # one sequence of the residual stream per rank
+@pytest.mark.parametrize("parallel,world,kw,model", [
+    pytest.param("tp", 8, {}, HEADS12, id="tp-8-kw0"),
+    pytest.param("dp", 8, {"tp": 4}, HEADS12, id="dp-8-kw1"),  # dp2 x tp4: 3 heads per rank
+    # one sequence of the residual stream per rank
+    pytest.param("tp", 8, {"tp_sequence_parallel": True, "batch": 8}, HEADS12, id="tp-8-kw2"),
+    pytest.param("tp", 2, {"tp_sequence_parallel": True}, GQA_ROPE_RMS_GLU, id="tp-2-sp-gqa_rope_rms_glu"),
+    pytest.param("tp", 2, {"tp_sequence_parallel": False}, GQA_ROPE_RMS_GLU, id="tp-2-gqa_rope_rms_glu"),
 ])
-def test_uneven_heads_match_single_process(parallel, world, kw):
+def test_uneven_heads_match_single_process(parallel, world, kw, model):
     """BASELINE.json config 3 (GPT-2 small at TP=8) needs 12 heads on 8 ranks: losses and the reassembled
     params of the uneven head split match the single-process run.  Adam eps 1e-4 (instead of 1e-8) keeps
     the update linear in near-zero gradients, so fp32 reduction-order noise is not amplified to +-lr
     and the params can be compared at fp32 rounding level (measured max |diff| ~1.3e-7)."""
-    kw = dict(kw, model=HEADS12, eps=1e-4)
-    single = _run("dp", 1, model=HEADS12, eps=1e-4, batch=kw.get("batch", 4))
+    kw = dict(kw, model=model, eps=1e-4)
+    single = _run("dp", 1, model=model, eps=1e-4, batch=kw.get("batch", 4))
     res = _run(parallel, world, **kw)
     assert "tp_sequence_parallel" not in kw or all(r["sp"] == kw["tp_sequence_parallel"] for r in res)
     assert res[0]["losses"] == pytest.approx(single[0]["losses"], rel=1e-5, abs=1e-5)
-    full = _full_params(res, model=HEADS12)
+    full = _full_params(res, model=model)
     ref = single[0]["params"]
     assert set(full) == set(ref)
     for n in ref:
