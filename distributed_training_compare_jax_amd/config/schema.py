@@ -106,6 +106,14 @@ are optional and default to the reference behaviour:
   follow.  Tensor parallelism splits the gate and the up slab each evenly (``ParamSpec.tp: glu_rows``).  Every dtype and
   layout with ``fwd_gemm_dtype: bf16`` (the FP8 / MXFP8 forwards are refused); the GEMM-fused LayerNorm (``DTC_LN_FUSE``)
   is off under it.  A checkpoint records the value.
+* ``ModelConfig.qk_norm`` (``none`` | ``rmsnorm``, default ``none``): ``rmsnorm`` normalises every query and key head
+  over ``head_dim`` before the rotation, ``z = x * rsqrt(mean(x^2) + layernorm_eps) * g`` (the Qwen3 / OLMo 2 form;
+  ``ops/qknorm.py``, ``csrc/qknorm.hip``: one in-place pass over ``qkv`` that also rotates under ``pos_emb: rope``, and its
+  transpose over ``dqkv``).  Two parameters per layer, ``h.*.qn.g`` and ``h.*.kn.g`` of ``[head_dim]``, initialised to
+  ones and shared by the layer's query / key heads (:meth:`ModelConfig.num_params` follows); V is untouched.  Both
+  dtypes, dp, pp, ZeRO-1, ``grad_accum``, ``doc_mask_token``, ``n_kv_heads``, every ``pos_emb`` / ``norm`` / ``mlp``; tensor
+  parallelism and the FP8 / MXFP8 forwards are refused, and so is a head_dim outside 32 / 64 / 128 on the GPU.  A
+  checkpoint records the value.
 """
 
 from __future__ import annotations
@@ -139,10 +147,13 @@ class ModelConfig:
     rope_theta: float = 10000.0  # rope: the angles are t * rope_theta**(-2i/head_dim)
     norm: str = "layernorm"  # layernorm (scale and bias) | rmsnorm (scale only, no mean: ops/rmsnorm.py)
     mlp: str = "gelu"  # gelu (fc2(gelu(fc1 x))) | swiglu (fc2(silu(gate x) * up x), fc1 = [gate; up]: ops/swiglu.py)
+    qk_norm: str = "none"  # none | rmsnorm (an RMSNorm with a learned gain on every Q and K head: ops/qknorm.py)
 
     def __post_init__(self):
         import math
 
+        if self.qk_norm not in ("none", "rmsnorm"):
+            raise ValueError(f"qk_norm={self.qk_norm!r}: expected 'none' or 'rmsnorm'")
         if self.pos_emb not in ("learned", "rope"):
             raise ValueError(f"pos_emb={self.pos_emb!r}: expected 'learned' or 'rope'")
         if self.norm not in ("layernorm", "rmsnorm"):
@@ -191,7 +202,8 @@ class ModelConfig:
         per_layer = (Q + D) * D + (Q + D) + D * F1 + F1 + F * D + D + 4 * D
         pos = T * D if self.pos_emb == "learned" else 0  # rope has no position table
         nb = (2 * L + 1) * D if self.norm == "rmsnorm" else 0  # rmsnorm has no norm biases
-        return V * D + pos + L * per_layer + 2 * D + D * V + V - nb
+        qn = 2 * L * self.head_dim if self.qk_norm == "rmsnorm" else 0  # the query and the key gain of every layer
+        return V * D + pos + L * per_layer + 2 * D + D * V + V - nb + qn
 
     def flops_per_token(self, causal: bool = True) -> float:
         """Matmul FLOPs per token, fwd+bwd: 6 * N_matmul + attention.  ``causal`` (default): the useful

@@ -35,10 +35,10 @@ FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-munsafe-fp-at
 DEBUG_FLAGS = ["-O1", "-g", "-DDTC_DEBUG", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
                "-Wno-unused-result"]
 DEBUG_OUT = os.path.join(PKG, "_dtc_kernels_debug.so")
-# per-file extra hipcc options (basename -> list).  rope.hip, rmsnorm.hip: plain fp32 multiplies and FMAs, no
-# packed-fp32 forms
+# per-file extra hipcc options (basename -> list).  rope.hip, rmsnorm.hip, qknorm.hip: plain fp32 multiplies and FMAs,
+# no packed-fp32 forms
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-FILE_FLAGS = {"rope.hip": _NO_PK_F32, "rmsnorm.hip": _NO_PK_F32}
+FILE_FLAGS = {"rope.hip": _NO_PK_F32, "rmsnorm.hip": _NO_PK_F32, "qknorm.hip": _NO_PK_F32}
 STATUS = {"kernels": None, "host": None}  # "compiled" | "reused" after build()
 
 

@@ -43,6 +43,7 @@ from ..ops import swiglu as SW
 from ..ops import fp8 as F8
 from ..ops import mxfp8 as MX
 from ..ops import ln_fused as LF
+from ..ops import qknorm as QN
 from ..ops import rope as R
 from ..ops import xent as X
 from ..ops.reduce import GradReducer
@@ -126,7 +127,9 @@ class StageLayout:
 class BlockCtx(NamedTuple):
     """What ``block_forward`` keeps of layer l for ``block_backward`` (``ctx[l]``).  ``y1`` / ``y2`` / ``qkv`` / ``o`` /
     ``u`` / ``gact`` hold the rows the GEMMs read (all of them under sequence parallelism), ``x`` / ``x2`` and the
-    norm statistics this rank's rows; ``mu1`` / ``mu2`` are None under ``rmsnorm``."""
+    norm statistics this rank's rows; ``mu1`` / ``mu2`` are None under ``rmsnorm``.  (Under ``qk_norm: rmsnorm`` the raw
+    Q | K columns and head statistics of the fused forward travel beside it as ``ctx[("qk", l)]``: this tuple keeps its
+    14 fields.)"""
 
     x: torch.Tensor
     y1: torch.Tensor
@@ -190,6 +193,7 @@ class GPTStage:
         self.eps = cfg.layernorm_eps
         self.rms = cfg.norm == "rmsnorm"  # every norm site goes through _norm / _add_norm / _ln_bwd
         self.glu = cfg.mlp == "swiglu"  # the bf16 MLP goes through _fc1 / _fc2_bwd
+        self.qkn = cfg.qk_norm == "rmsnorm"  # _qk_fwd / _qk_bwd: the head norm and the rotation in one pass
         # Deferred weight gradients (set_wgrad_group): the dgrad chain runs alone and every (dY, X, dW, db)
         # of wgrad_group consecutive layers (0 = the whole stage, + the lm_head) goes out as ONE grouped
         # launch of whole 256^2 tiles (ops/gemm.py wgrad_group)
@@ -455,6 +459,29 @@ class GPTStage:
             R.rope_(qkv.view(batch, qkv.shape[0] // batch, -1), self.rope_tab, self.heads_local,
                     self.kv_heads_local or self.heads_local, inverse)
 
+    def _qk_fwd(self, qkv: torch.Tensor, batch: int, l: int, ctx: Dict):
+        """What sits between the qkv GEMM and the attention, in place on the local Q and K heads of ``qkv [batch * T, .]``:
+        the rotation alone (:meth:`_rope`), or under ``qk_norm: rmsnorm`` the head norm, its gains ``qn.g`` / ``kn.g`` and
+        the rotation in one pass (``ops/qknorm.py``; no table under learned positions), which leaves ``(qk_raw, rstd)``
+        in ``ctx[("qk", l)]`` for :meth:`_qk_bwd`."""
+        if not self.qkn:
+            return self._rope(qkv, batch)
+        f, p = self.flat, f"h.{l}."
+        ctx[("qk", l)] = QN.qknorm_rope_fwd_(qkv.view(batch, qkv.shape[0] // batch, -1), self.rope_tab, f.p(p + "qn.g"),
+                                             f.p(p + "kn.g"), self.heads_local, self.kv_heads_local or self.heads_local,
+                                             self.eps)[1:]
+
+    def _qk_bwd(self, dqkv: torch.Tensor, batch: int, l: int, ctx: Dict, beta: float):
+        """The transpose of :meth:`_qk_fwd`, in place on ``dqkv`` right after the attention backward; under ``qk_norm:
+        rmsnorm`` it also produces the two gain gradients (partials finished by the layer's batched reduction)."""
+        if not self.qkn:
+            return self._rope(dqkv, batch, inverse=True)
+        f, p = self.flat, f"h.{l}."
+        raw, rstd = ctx.pop(("qk", l))
+        QN.qknorm_rope_bwd_(dqkv.view(batch, dqkv.shape[0] // batch, -1), self.rope_tab, raw, rstd, f.p(p + "qn.g"),
+                            f.p(p + "kn.g"), self.heads_local, self.kv_heads_local or self.heads_local, f.g(p + "qn.g"),
+                            f.g(p + "kn.g"), beta, red=self.red)
+
     # ------------------------------------------------------------------ embed
     def embed_forward(self, ids: torch.Tensor, step: torch.Tensor, row0: int, ctx: Dict,
                       want_keys: bool = True, keys: Optional[torch.Tensor] = None,
@@ -572,7 +599,7 @@ class GPTStage:
         y1 = self._rows(y1l)
         T = y1.shape[0] // batch
         qkv = self._linear(y1, y1q, p + "qkv")
-        self._rope(qkv, batch)
+        self._qk_fwd(qkv, batch, l, ctx)
         o, lse = A.attn_fwd(qkv.view(batch, T, -1), self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local)
         o = o.view(batch * T, -1)
         x2, (y2l, mu2, rs2, y2q) = self._row_resid_norm(o, None, p + "out", x, p + "ln2", self._ln_site(l, 0, False),
@@ -637,7 +664,7 @@ class GPTStage:
                                    out_dtype=self.act_dtype, pair=False)
         dqkv = A.attn_bwd(c.qkv.view(batch, T, -1), c.o.view(batch, T, -1), c.lse, do.view(batch, T, -1),
                           self.heads_local, doc=ctx.get("doc"), n_kv_heads=self.kv_heads_local).view(batch * T, -1)
-        self._rope(dqkv, batch, inverse=True)
+        self._qk_bwd(dqkv, batch, l, ctx, beta)
         wtq = f.wt(p + "qkv.w")
         if self._fuse_bwd and wtq is not None:
             bg = self._prev_fc2b(l)
@@ -751,6 +778,7 @@ class GPTStage:
             x = self.block_forward(l, x, batch, ctx)
             if not keep:
                 del ctx[l]
+                ctx.pop(("qk", l), None)
         return x
 
     @contextlib.contextmanager

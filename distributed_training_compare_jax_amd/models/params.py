@@ -23,6 +23,9 @@ layer axis by ``nn.scan`` (``GPTModel.py:58-64``), then the final ``LayerNorm`` 
 * Grouped-query attention (``ModelConfig.n_kv_heads``): ``qkv.w`` has ``(H + 2 Hkv) * hd`` rows -- H query heads, Hkv
   key heads, Hkv value heads -- and TP shards whole GROUPS: each slab is split evenly by its own heads, which keeps
   every query head on the rank of its K/V head iff ``Hkv % tp == 0`` (anything else is refused by name).
+* QK-norm (``ModelConfig.qk_norm: rmsnorm``): two gains per layer, ``qn.g`` and ``kn.g`` of ``[head_dim]``, shared by the
+  layer's query / key heads and replicated over TP (tensor parallelism is refused by the engine: a rank's gradients
+  cover its own heads only).
 
 Flat-buffer order = the order backward produces gradients (head → layers L-1..0 →
 embeddings), so DP buckets are contiguous ranges that become ready in sequence.
@@ -84,6 +87,11 @@ def layer_param_specs(cfg: ModelConfig, l: int) -> List[ParamSpec]:
         glu = {p + "fc1.w": ParamSpec(p + "fc1.w", (2 * F, D), "dense", D, "glu_rows", l, True),
                p + "fc1.b": ParamSpec(p + "fc1.b", (2 * F,), "zeros", D, "glu_rows", l, True)}
         specs = [glu.get(s.name, s) for s in specs]
+    if cfg.qk_norm == "rmsnorm":  # the query and the key gain, shared by the layer's heads: produced by the backward
+        # after the attention's, i.e. after out.b and before qkv.w (ops/qknorm.py)
+        hd, i = cfg.head_dim, [s.name for s in specs].index(p + "qkv.w")
+        specs[i:i] = [ParamSpec(p + "qn.g", (hd,), "ones", hd, "rep", l, True),
+                      ParamSpec(p + "kn.g", (hd,), "ones", hd, "rep", l, True)]
     return specs
 
 

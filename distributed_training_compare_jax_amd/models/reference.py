@@ -127,6 +127,9 @@ def oracle_logits(cfg: ModelConfig, params: dict, ids: torch.Tensor, seed: int, 
         Hkv = cfg.kv_heads
         q, k, v = qkv.split([H * hd, Hkv * hd, Hkv * hd], -1)
         q, k = q.view(B, T, H, hd), k.view(B, T, Hkv, hd)
+        if cfg.qk_norm == "rmsnorm":  # an RMSNorm over head_dim of every head, one gain per layer and kind (ops/qknorm.py)
+            q = q * torch.rsqrt(q.pow(2).mean(-1, keepdim=True) + eps) * p("qn.g")
+            k = k * torch.rsqrt(k.pow(2).mean(-1, keepdim=True) + eps) * p("kn.g")
         if rope:
             q, k = rot(q), rot(k)
         k, v = (t.reshape(B, T, Hkv, hd).repeat_interleave(H // Hkv, 2) for t in (k, v))

@@ -180,6 +180,12 @@ def _declare(lib):
         "dtc_embed_sq_slots": ([i, i, i, i], l),
         # rotary position embeddings (csrc/rope.hip): x, tab, B, T, H, Hkv, head_dim, tab_rows, dtype, inverse, stream
         "dtc_rope": ([vp, vp, i, i, i, i, i, i, i, i, vp], i),
+        # QK-norm fused with the rotation (csrc/qknorm.hip): fwd x, tab (null: no rotation), gq, gk, qk_raw, rstd, B, T,
+        # H, Hkv, head_dim, tab_rows, eps, dtype, stream; bwd dy, tab, qk_raw, rstd, gq, gk, dgq, dgk, B, T, H, Hkv,
+        # head_dim, tab_rows, dtype, accumulate, ws, ws_bytes, defer, stream
+        "dtc_qknorm_fwd": ([vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, i, vp], i),
+        "dtc_qknorm_bwd": ([vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, l, i, vp], i),
+        "dtc_qknorm_bwd_workspace_bytes": ([i, i], l),
         "dtc_attn_fwd": ([vp, vp, vp, i, i, i, i, i, f, vp], i),
         "dtc_attn_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, l, vp], i),
         "dtc_attn_bwd_workspace_bytes": ([i, i, i, i], l),

@@ -182,6 +182,21 @@ class Engine:
         if model_cfg.mlp == "swiglu" and train_cfg.fwd_gemm_dtype != "bf16":
             raise ValueError(f"mlp=swiglu cannot be combined with fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the FP8 and "
                              "MXFP8 forwards fuse their quantiser into the fc1 GELU epilogue)")
+        # qk_norm: rmsnorm (ops/qknorm.py) runs under dp, pp, ZeRO-1, both dtypes and every pos_emb / norm / mlp; what it
+        # does not cover is refused here, by name
+        if model_cfg.qk_norm == "rmsnorm":
+            why = None
+            hd = model_cfg.d_model // model_cfg.n_heads
+            if tp > 1:
+                why = (f"tp={tp} (tensor parallelism: the gains are replicated but each rank's gradients cover only its "
+                       "own heads; the follow-up sums them over the TP group)")
+            elif train_cfg.fwd_gemm_dtype != "bf16":
+                why = f"fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the FP8 / MXFP8 forwards have not been run with it)"
+            elif dinfo.device.type == "cuda" and hd not in (32, 64, 128):
+                why = (f"head_dim {hd} on the GPU (d_model {model_cfg.d_model} / n_heads {model_cfg.n_heads}): the QK-norm "
+                       "kernels are instantiated for head_dim 32, 64 and 128")
+            if why:
+                raise ValueError(f"qk_norm=rmsnorm cannot be combined with {why}")
         # eval_every: the held-out evaluation (evaluate) -- what it does not cover is refused here, by name
         if train_cfg.eval_every > 0:
             if pp > 1:

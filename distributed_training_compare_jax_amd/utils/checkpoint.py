@@ -52,7 +52,7 @@ def save(eng, output_dir: str, step: int):
                 layers=[lr.layers.start, lr.layers.stop] if lr is not None else None,
                 vocab_size=int(eng.mcfg.vocab_size), padded_vocab=int(eng.mcfg.padded_vocab),
                 n_kv_heads=int(eng.mcfg.kv_heads), pos_emb=eng.mcfg.pos_emb, rope_theta=float(eng.mcfg.rope_theta),
-                norm=eng.mcfg.norm, mlp=eng.mcfg.mlp)
+                norm=eng.mcfg.norm, mlp=eng.mcfg.mlp, qk_norm=eng.mcfg.qk_norm)
     with open(os.path.join(d, f"meta_rank{m.rank}.json"), "w") as fh:
         json.dump(meta, fh)
 
@@ -153,6 +153,11 @@ def source_rank(eng, metas: Dict[int, dict]) -> int:
     if mlp_ck != mlp_now:
         raise ValueError(f"checkpoint was written with mlp={mlp_ck!r}, this run has mlp={mlp_now!r}: resume with "
                          "the value that wrote it")
+    # the QK-norm decides whether the head gains exist and what the qkv weights mean (before the field: none)
+    qkn_ck, qkn_now = m0.get("qk_norm", "none"), eng.mcfg.qk_norm
+    if qkn_ck != qkn_now:
+        raise ValueError(f"checkpoint was written with qk_norm={qkn_ck!r}, this run has qk_norm={qkn_now!r}: resume "
+                         "with the value that wrote it")
     want = (mesh.dp_idx, mesh.tp_idx, mesh.pp_idx)
     src = None
     for r, m in metas.items():
