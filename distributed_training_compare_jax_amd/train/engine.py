@@ -172,18 +172,22 @@ class Engine:
                        "kernels are the 32-row family, head_dim 64 or 128")
             if why:
                 raise ValueError(f"n_kv_heads={model_cfg.kv_heads} cannot be combined with {why}")
-        # norm: rmsnorm (ops/rmsnorm.py) runs under every layout, dtype and schedule; what it does not cover is refused
-        # here, by name
+        # norm: rmsnorm (ops/rmsnorm.py) runs under every layout, dtype and schedule (tensor parallelism:
+        # tests/test_dist_gpu.py GQA_ROPE_RMS_GLU; accumulation, dp, ZeRO-1, the P2P transports, every pipeline schedule,
+        # resume, evaluation, the document mask and d_model 2048, both dtypes: tests/test_modern_block_layouts_gpu.py);
+        # what it does not cover is refused here, by name
         if model_cfg.norm == "rmsnorm" and train_cfg.fwd_gemm_dtype != "bf16":
             raise ValueError(f"norm=rmsnorm cannot be combined with fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the MXFP8 "
                              "quantiser is fused into the LayerNorm kernel, and the FP8 forwards have not been run with it)")
-        # mlp: swiglu (ops/swiglu.py) runs under every layout, dtype and schedule; what it does not cover is refused
-        # here, by name
+        # mlp: swiglu (ops/swiglu.py) runs under every layout, dtype and schedule (the same two files hold it, with the
+        # fused pair at K = 2048 under DTC_SWIGLU_FUSE=2); what it does not cover is refused here, by name
         if model_cfg.mlp == "swiglu" and train_cfg.fwd_gemm_dtype != "bf16":
             raise ValueError(f"mlp=swiglu cannot be combined with fwd_gemm_dtype={train_cfg.fwd_gemm_dtype} (the FP8 and "
                              "MXFP8 forwards fuse their quantiser into the fc1 GELU epilogue)")
-        # qk_norm: rmsnorm (ops/qknorm.py) runs under dp, pp, ZeRO-1, both dtypes and every pos_emb / norm / mlp; what it
-        # does not cover is refused here, by name
+        # qk_norm: rmsnorm (ops/qknorm.py) runs under dp, pp, ZeRO-1, both dtypes and every pos_emb / norm / mlp (every
+        # pos_emb / norm / mlp: tests/test_qknorm_engine_gpu.py; dp, pp gpipe / 1f1b / zb with and without the split
+        # head, ZeRO-1 and the P2P transports in fp32 and bf16: tests/test_modern_block_layouts_gpu.py, on the CPU
+        # tests/test_modern_block_layouts_cpu.py); what it does not cover is refused here, by name
         if model_cfg.qk_norm == "rmsnorm":
             why = None
             hd = model_cfg.d_model // model_cfg.n_heads
